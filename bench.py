@@ -2,7 +2,7 @@
 """bench.py — Krylov iterations/second on the 4096 x 4096 blur, with the blur-matvec HBM roofline and a same-box
 CPU baseline, as one JSON line (driver contract).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N > 1: one rank per GPU.  Either a launcher started the ranks (`python -m torch.distributed.run --nproc-per-node N ...
 bench.py --gpus N`: RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment), or — plain `python bench.py --gpus N`
@@ -37,13 +37,27 @@ EXTRAS_BUDGET_S = 420
 # in the JSON line ("run_in_iters"), and part of neither `steps` nor `warmup`.
 RUN_IN_ITERS = 400
 HBM_PEAK_GBPS = 8000.0     # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
+# --dump-outputs: the last iterate is written whole up to this many entries, above it as a sample of this many entries at
+# fixed, seeded positions (4096^2: 16 MiB of the 64 MiB iterate); divided among the ranks when there are several
+DUMP_X_MAX = 1 << 22
+DUMP_SEED = 0
+
+
+def positive_int(s):
+    v = int(s)
+    if v < 1:
+        raise argparse.ArgumentTypeError(f"must be >= 1, got {v}")
+    return v
 
 
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=100)
+    ap.add_argument("--steps", type=positive_int, default=100, help="timed iterations (`ms_per_step` is their mean)")
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed loop computed (its last iterate x, whole or sampled, and "
+                         "the per-iteration CGLS scalars) as DIR/<name>.npy")
     ap.add_argument("--size", type=int, default=4096, help="image side of the blur workload")
     ap.add_argument("--workload", default="blur_cgls", choices=["blur_cgls"])
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -202,6 +216,23 @@ def emit_json(fd, res):
     os.write(fd, (json.dumps(res) + "\n").encode())
 
 
+def dump_outputs(out_dir, rank, world, x, rows):
+    """--dump-outputs: what a caller of the timed loop receives after its last step — the iterate x (float32; whole, or
+    `x_sample` = x at DUMP_X_MAX sorted positions drawn with DUMP_SEED) and `cgls_scalars` (float64, one row per iteration of
+    warm-up + timed loop: delta, gamma, ||x||^2, ||x - x_prev||^2, ||x - x_true||^2 (0: no x_true given)).  Several ranks: one
+    set per rank, suffixed _rank<r>.  Inputs are seeded, so the same arguments give the same inputs on every run."""
+    os.makedirs(out_dir, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    n, cap = x.numel(), DUMP_X_MAX // world
+    if n <= cap:
+        name, xs = "x", x
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=cap, replace=False))
+        name, xs = "x_sample", x[torch.from_numpy(idx).to(x.device)]
+    np.save(os.path.join(out_dir, name + sfx + ".npy"), xs.detach().to("cpu", torch.float32).numpy())
+    np.save(os.path.join(out_dir, "cgls_scalars" + sfx + ".npy"), np.asarray(rows, dtype=np.float64))
+
+
 def run_blur_cgls(args, rank, world, json_fd=1):
     from trips_py_amd.operators import Blur2D
     from trips_py_amd.problems import gauss_psf
@@ -350,6 +381,8 @@ def run_blur_cgls(args, rank, world, json_fd=1):
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         b_host = b.detach().to("cpu")
         cpu_jobs.append((lambda v: res.__setitem__("cpu_baseline", v), lambda: cpu_baseline_cgls(psf, N, b_host, args.cpu_iters)))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, world, run.x_cur, rows)
     del run
     torch.cuda.empty_cache()
     if not args.no_extras:

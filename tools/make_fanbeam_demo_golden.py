@@ -15,7 +15,9 @@ notebook's JSON, crops the axes area (the opaque pixels), and
     it is (218 x 165, uint8) — the test renders the candidate matrix to the same raster.
 
 Output: tests/golden/fanbeam_demo_image.npz — numbers only (grey levels decoded from images + the phantom array that
-`trips.utilities.phantoms.tectonic(32)` returns when the reference is imported here).
+`trips.utilities.phantoms.tectonic(32)` returns when the reference is imported here) — and, beside it,
+tests/golden/fanbeam_demo_notebook_png.npz: the three PNG outputs themselves (bytes as uint8 arrays), so that the decoding
+can be repeated without the reference tree (`decode`, tests/test_dropin_container.py).
 usage: python3 tools/make_fanbeam_demo_golden.py [out.npz]"""
 import base64
 import io
@@ -31,13 +33,27 @@ NB = os.path.join(REF, "demos", "demo_Tomo_small_scale.ipynb")
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def cell_png(nb, source_starts):
+CELLS = {"AA_png": "plt.imshow(AA)", "b_png": "plt.imshow(b)", "xtrue_png": "plt.imshow(x_true.reshape((nx, ny)))"}
+PNG_FIXTURE = os.path.join(REPO, "tests", "golden", "fanbeam_demo_notebook_png.npz")
+
+
+def cell_png_bytes(nb, source_starts):
     for c in nb["cells"]:
         if c["cell_type"] == "code" and "".join(c["source"]).startswith(source_starts):
             for o in c.get("outputs", []):
                 if "image/png" in o.get("data", {}):
-                    return np.asarray(Image.open(io.BytesIO(base64.b64decode(o["data"]["image/png"]))).convert("RGBA"))
+                    return base64.b64decode(o["data"]["image/png"])
     raise KeyError(source_starts)
+
+
+def notebook_pngs(path=NB):
+    """The PNG bytes of the three cell outputs, keyed as in PNG_FIXTURE."""
+    nb = json.load(open(path))
+    return {k: cell_png_bytes(nb, src) for k, src in CELLS.items()}
+
+
+def rgba(png):
+    return np.asarray(Image.open(io.BytesIO(png)).convert("RGBA"))
 
 
 def crop_axes(rgba):
@@ -63,22 +79,30 @@ def sample_centres(grey, rows, cols):
     return out
 
 
-def main(out):
-    nb = json.load(open(NB))
-    g_b = crop_axes(cell_png(nb, "plt.imshow(b)"))
-    g_x = crop_axes(cell_png(nb, "plt.imshow(x_true.reshape((nx, ny)))"))
-    g_A = crop_axes(cell_png(nb, "plt.imshow(AA)"))
+def decode(pngs):
+    """Grey-level arrays and layout of the fixture from the three PNG outputs (everything but the phantom)."""
+    g_b = crop_axes(rgba(pngs["b_png"]))
+    g_x = crop_axes(rgba(pngs["xtrue_png"]))
+    g_A = crop_axes(rgba(pngs["AA_png"]))
     views, nx = 30, 32
     p = int(np.sqrt(2) * nx)
     sino = sample_centres(g_b, views, p)          # add_noise reshapes to (self.p, self.q) = (views, rows / views) after gen_data
     xim = sample_centres(g_x, nx, nx)
+    return dict(sino_grey=sino, xtrue_grey=xim, AA_grey=g_A, views=np.int64(views), nx=np.int64(nx), n_det=np.int64(p),
+                AA_shape=np.array([views * p, nx * nx]))
+
+
+def main(out):
+    pngs = notebook_pngs()
+    np.savez_compressed(PNG_FIXTURE, **{k: np.frombuffer(v, dtype=np.uint8) for k, v in pngs.items()})
+    d = decode(pngs)
     sys.path.insert(0, REF)
     from trips.utilities import phantoms           # imports without pylops / astra
-    phantom = np.asarray(phantoms.tectonic(nx), dtype=np.float64)
-    np.savez_compressed(out, sino_grey=sino, xtrue_grey=xim, AA_grey=g_A, phantom=phantom,
-                        views=np.int64(views), nx=np.int64(nx), n_det=np.int64(p), AA_shape=np.array([views * p, nx * nx]))
-    print(f"wrote {out}: sino_grey {sino.shape}, xtrue_grey {xim.shape}, AA_grey {g_A.shape}; "
-          f"phantom levels {np.unique(phantom)}, image levels {np.unique(xim)}")
+    phantom = np.asarray(phantoms.tectonic(int(d["nx"])), dtype=np.float64)
+    np.savez_compressed(out, sino_grey=d["sino_grey"], xtrue_grey=d["xtrue_grey"], AA_grey=d["AA_grey"], phantom=phantom,
+                        views=d["views"], nx=d["nx"], n_det=d["n_det"], AA_shape=d["AA_shape"])
+    print(f"wrote {PNG_FIXTURE} and {out}: sino_grey {d['sino_grey'].shape}, xtrue_grey {d['xtrue_grey'].shape}, "
+          f"AA_grey {d['AA_grey'].shape}; phantom levels {np.unique(phantom)}, image levels {np.unique(d['xtrue_grey'])}")
 
 
 if __name__ == "__main__":
