@@ -1025,44 +1025,111 @@ class FanBeam2D(_Op):
         self.pitch = (self.sod + self.odd) / self.sod if pitch is None else float(pitch)
         self.shape = (len(self.angles) * self.nd, self.N * self.N)
         self._M = None
+        self._cs = None
+
+    def _rays(self, ray_idx):
+        """source (sx, sy), direction source -> detector-pixel centre (dx, dy) and its length L of the rays a * nd + d."""
+        if self._cs is None:        # per angle as scalars, as the clip always took them
+            self._cs = (np.array([np.cos(th) for th in self.angles]), np.array([np.sin(th) for th in self.angles]))
+        ray_idx = np.asarray(ray_idx, dtype=np.int64)
+        a, d = ray_idx // self.nd, ray_idx % self.nd
+        ct, st = self._cs[0][a], self._cs[1][a]
+        sx, sy = self.sod * st, -self.sod * ct
+        off = (d - 0.5 * (self.nd - 1)) * self.pitch
+        ex, ey = -self.odd * st + off * ct, self.odd * ct + off * st
+        dx, dy = ex - sx, ey - sy
+        return sx, sy, dx, dy, np.hypot(dx, dy)
+
+    def _pixel_box(self, pix_idx):
+        """[x0, x1] x [y0, y1]: the squares of pixels r * N + c."""
+        half = 0.5 * self.N
+        rr, cc = np.divmod(np.asarray(pix_idx, dtype=np.int64), self.N)
+        y1 = half - rr
+        return cc - half, cc + 1 - half, y1 - 1.0, y1
+
+    @staticmethod
+    def _clip(sx, sy, dx, dy, L, x0, x1, y0, y1):
+        """Length of the segment source -> detector-pixel centre (t in [0, 1]) inside the square [x0, x1] x [y0, y1]; rays and
+        squares broadcast against each other.  The one clipping code of matrix(), rows() and cols()."""
+        shape = np.broadcast(sx, x0).shape
+        t0, t1 = np.zeros(shape), np.ones(shape)
+        for (lo, hi, s0, dd, axis) in ((x0, x1, sx, dx, 0), (y0, y1, sy, dy, 1)):
+            # axis-parallel RELATIVE to the ray's length: at t = pi/2, pi, 3 pi/2 the float64 sine / cosine leave dd ~ 1e-16 L,
+            # an absolute threshold let rays of N > 40 cross a pixel boundary halfway along (test_gpu_fanbeam_accuracy: views
+            # pi/2 with p odd); and such a ray's coordinate is on the boundary up to that same rounding (snapped below 1e-9)
+            ok = np.abs(dd) > 1e-14 * L
+            s0p = np.where(np.abs(s0 - np.round(s0)) < 1e-9, np.round(s0), s0)
+            with np.errstate(divide="ignore", invalid="ignore"):
+                ta, tb = (lo - s0) / dd, (hi - s0) / dd
+            t0 = np.where(ok, np.maximum(t0, np.minimum(ta, tb)), t0)
+            t1 = np.where(ok, np.minimum(t1, np.maximum(ta, tb)), t1)
+            if axis == 0:       # axis-parallel ray: a ray running exactly ALONG a pixel boundary belongs to ONE
+                # side — the pixel with the larger column (row) index, as a `floor(c + 0.5)` pixel choice gives
+                # it; the reference's ASTRA sinogram of the 32^2 demo (tests/golden/fanbeam_demo_image.npz: view 0,
+                # detector 22 runs along x = 0) shows one column's mass there, not two
+                t1 = np.where(~ok & ((s0p < lo) | (s0p >= hi)), -1.0, t1)
+            else:               # rows grow downwards: the larger row index is the pixel BELOW the boundary
+                t1 = np.where(~ok & ((s0p <= lo) | (s0p > hi)), -1.0, t1)
+        return (t1 - t0) * L
 
     def matrix(self):
         if self._M is None:
-            N, nd, half = self.N, self.nd, 0.5 * self.N
-            rr, cc = np.meshgrid(np.arange(N), np.arange(N), indexing="ij")
-            x0, x1 = (cc - half).reshape(-1), (cc + 1 - half).reshape(-1)
-            y1 = (half - rr).reshape(-1)
-            y0 = y1 - 1.0
+            box = self._pixel_box(np.arange(self.N * self.N))
             rows, cols, vals = [], [], []
-            for a, th in enumerate(self.angles):
-                ct, st = np.cos(th), np.sin(th)
-                sx, sy = self.sod * st, -self.sod * ct
-                for d in range(nd):
-                    off = (d - 0.5 * (nd - 1)) * self.pitch
-                    ex, ey = -self.odd * st + off * ct, self.odd * ct + off * st
-                    dx, dy = ex - sx, ey - sy
-                    L = np.hypot(dx, dy)
-                    t0 = np.zeros(N * N)
-                    t1 = np.ones(N * N)
-                    for (lo, hi, s0, dd, axis) in ((x0, x1, sx, dx, 0), (y0, y1, sy, dy, 1)):
-                        if abs(dd) > 1e-14:
-                            ta, tb = (lo - s0) / dd, (hi - s0) / dd
-                            t0 = np.maximum(t0, np.minimum(ta, tb))
-                            t1 = np.minimum(t1, np.maximum(ta, tb))
-                        elif axis == 0:     # axis-parallel ray: a ray running exactly ALONG a pixel boundary belongs to ONE
-                            # side — the pixel with the larger column (row) index, as a `floor(c + 0.5)` pixel choice gives
-                            # it; the reference's ASTRA sinogram of the 32^2 demo (tests/golden/fanbeam_demo_image.npz: view 0,
-                            # detector 22 runs along x = 0) shows one column's mass there, not two
-                            t1 = np.where((s0 < lo) | (s0 >= hi), -1.0, t1)
-                        else:               # rows grow downwards: the larger row index is the pixel BELOW the boundary
-                            t1 = np.where((s0 <= lo) | (s0 > hi), -1.0, t1)
-                    ln = (t1 - t0) * L
-                    nz = np.nonzero(ln > 1e-12)[0]
-                    rows.append(np.full(nz.size, a * nd + d))
-                    cols.append(nz)
-                    vals.append(ln[nz])
+            for ray in range(self.shape[0]):
+                ln = self._clip(*self._rays(ray), *box)
+                nz = np.nonzero(ln > 1e-12)[0]
+                rows.append(np.full(nz.size, ray))
+                cols.append(nz)
+                vals.append(ln[nz])
             self._M = sp.coo_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))), shape=self.shape).tocsr()
         return self._M
+
+    def rows(self, ray_idx):
+        """matrix()[ray_idx] (CSR) without the matrix: each ray clipped by _clip against a window of pixels around it — in every
+        row (steep ray) or column (shallow ray) the columns (rows) the line passes there, and one more on either side."""
+        N, half = self.N, 0.5 * self.N
+        ray_idx = np.asarray(ray_idx, dtype=np.int64).reshape(-1)
+        t = np.arange(N)
+        out_r, out_c, out_v = [], [], []
+        for k, ray in enumerate(ray_idx):
+            sx, sy, dx, dy, L = (float(v) for v in self._rays(ray))
+            steep = abs(dy) >= abs(dx)
+            if steep:       # the line on the edges y = half - t, half - t - 1 of row t, as a column coordinate x + half
+                u0, u1 = sx + (half - t - sy) * (dx / dy) + half, sx + (half - t - 1 - sy) * (dx / dy) + half
+            else:           # on the edges x = t - half, t + 1 - half of column t, as a row coordinate half - y
+                u0, u1 = half - sy - (t - half - sx) * (dy / dx), half - sy - (t + 1 - half - sx) * (dy / dx)
+            lo = np.floor(np.minimum(u0, u1)).astype(np.int64) - 1
+            hi = np.floor(np.maximum(u0, u1)).astype(np.int64) + 1
+            other = lo[:, None] + np.arange(int((hi - lo).max()) + 1)[None, :]
+            tt = np.broadcast_to(t[:, None], other.shape)
+            keep = (other >= 0) & (other < N) & (other <= hi[:, None])
+            pix = np.unique((tt * N + other if steep else other * N + tt)[keep])
+            ln = self._clip(sx, sy, dx, dy, L, *self._pixel_box(pix))
+            nz = ln > 1e-12
+            out_r.append(np.full(int(nz.sum()), k))
+            out_c.append(pix[nz])
+            out_v.append(ln[nz])
+        return sp.csr_matrix((np.concatenate(out_v), (np.concatenate(out_r), np.concatenate(out_c))), shape=(ray_idx.size, self.shape[1]))
+
+    def cols(self, pix_idx):
+        """matrix()[:, pix_idx] (CSC) without the matrix: every ray clipped by _clip against each pixel, vectorised over the rays."""
+        pix_idx = np.asarray(pix_idx, dtype=np.int64).reshape(-1)
+        rays = self._rays(np.arange(self.shape[0]))
+        out_r, out_c, out_v = [], [], []
+        for k, p in enumerate(pix_idx):
+            ln = self._clip(*rays, *self._pixel_box(p))
+            nz = np.nonzero(ln > 1e-12)[0]
+            out_r.append(nz)
+            out_c.append(np.full(nz.size, k))
+            out_v.append(ln[nz])
+        return sp.csc_matrix((np.concatenate(out_v), (np.concatenate(out_r), np.concatenate(out_c))), shape=(self.shape[0], pix_idx.size))
+
+    def slope(self, ray_idx):
+        """|M| of the rays a * nd + d: the slope in index coordinates in fanbeam2d.hip's row-march sense — columns per row for a
+        steep ray (|dy| >= |dx|), rows per column for a shallow one; <= 1."""
+        _, _, dx, dy, _ = self._rays(ray_idx)
+        return np.minimum(np.abs(dx), np.abs(dy)) / np.maximum(np.abs(dx), np.abs(dy))
 
     def _fwd(self, x):
         return self.matrix() @ x

@@ -333,6 +333,46 @@ def test_fanbeam_oracle_invariants():
     assert abs(np.dot(A @ x, y) - np.dot(x, A.T @ y)) < 1e-12 * np.linalg.norm(x) * np.linalg.norm(y) * N
 
 
+@pytest.mark.parametrize("geom", ["default", "odd_p", "pitch0.5", "pitch3", "inner_detector", "full_turn"])
+def test_fanbeam_oracle_row_and_column_samplers_are_the_matrix(geom):
+    """FanBeam2D.rows / .cols (the float64 reference of tests/test_gpu_fanbeam_accuracy.py at sizes where matrix() is out of
+    reach) return matrix()'s rows and columns to the bit, through the same clipping code: the default geometry; an odd
+    detector count with N even (rays along pixel boundaries: the tie rule pinned to the ASTRA images below); a fine and a
+    coarse detector; a detector inside the circumscribed circle; angles over [0, 2 pi) and negative ones.  slope() is the
+    row-march's |M|: a steep ray (shallow: transposed) meets at most two columns per row and |M| N of them in all."""
+    N, ang, kw = 16, np.linspace(0, np.pi, 8, endpoint=False), {}
+    if geom == "odd_p":
+        kw = {"n_det": 23}
+    elif geom == "pitch0.5":
+        N, ang, kw = 14, ang + 0.1, {"pitch": 0.5}
+    elif geom == "pitch3":
+        N, ang, kw = 14, ang + 0.05, {"pitch": 3.0, "n_det": 9}
+    elif geom == "inner_detector":
+        kw = {"odd": 0.5 * N}
+    elif geom == "full_turn":
+        ang = np.concatenate([np.linspace(0, 2 * np.pi, 8, endpoint=False) + 0.013, [-0.4, -np.pi / 2, -2.9]])
+    A = O.FanBeam2D(N, ang, **kw)
+    M = A.matrix()
+    rays, pix = np.arange(A.shape[0]), np.arange(A.shape[1])
+    R, C = A.rows(rays), A.cols(pix)
+    for S in (R.tocsr(), C.tocsr()):
+        assert S.shape == M.shape and S.nnz == M.nnz and (S != M).nnz == 0
+        assert np.array_equal(S.indptr, M.indptr) and np.array_equal(S.indices, M.indices) and np.array_equal(S.data, M.data)
+    sub_r, sub_c = rays[::5], pix[7::11]                    # any subset, any order: the same rows / columns
+    assert (A.rows(sub_r[::-1]) != M[sub_r[::-1]]).nnz == 0 and (A.cols(sub_c[::-1]) != M[:, sub_c[::-1]]).nnz == 0
+    if geom == "odd_p":                                     # the boundary rays are there: view 0 / 4, detector 11 runs along x = 0 / y = 0
+        assert np.array_equal(M[11].nonzero()[1] % N, np.full(N, N // 2))
+        assert np.array_equal(M[4 * 23 + 11].nonzero()[1] // N, np.full(N, N // 2))
+    slope = A.slope(rays)
+    assert np.all(slope <= 1.0)
+    if geom != "inner_detector":                            # (a detector inside the image cuts rays short)
+        _, _, dx, dy, _ = A._rays(rays)
+        for ray in rays[np.asarray(M.sum(axis=1)).reshape(-1) > 0]:
+            r, c = np.divmod(M[ray].nonzero()[1], N)
+            t, o = (r, c) if abs(dy[ray]) >= abs(dx[ray]) else (c, r)
+            assert np.bincount(t).max() <= 2 and o.max() - o.min() <= np.ceil(slope[ray] * N) + 1
+
+
 def test_fanbeam_oracle_vs_the_astra_outputs_the_reference_holds():
     """The only ASTRA outputs in the reference tree: the rendered fan-beam matrix `AA` and noisy sinogram `b` of the tectonic
     32^2, 30-view demo (demos/demo_Tomo_small_scale.ipynb:145,179; geometry Tomography.py:53-88, phantom phantoms.py:67),

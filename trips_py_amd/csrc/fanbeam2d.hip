@@ -17,7 +17,8 @@
 // (Shallow rays: the same with rows and columns exchanged.)  {X0, M, len, class} per ray is tabulated once per operator in
 // float64 and stored in FIXED POINT (X0 64 bits, M 32 bits, 30 fraction bits: 16 bytes per ray), so that a step's position
 // X0 + r M is exact integer arithmetic.  Lengths come out of pixel-sized quantities, not out of differences of ray parameters
-// along a ~4N-long segment as in a Siddon traversal, and carry no error that grows with N: agreement with the brute-force float64
+// along a ~4N-long segment as in a Siddon traversal; what grows with N is M's rounding, r 2^-31 of position, 1/|M| times that in a
+// weight (tests/test_gpu_fanbeam_accuracy.py: every weight within len (7 2^-24 + (4 + r) 2^-31 / |M|)): agreement with the brute-force float64
 // oracle at 1e-5 on white noise (Siddon pair: 1e-4; the same row-march in fp32 positions: 1.5e-5 at N = 132 and growing).
 // Forward: one thread per ray marches the N rows (columns), two taps per step, shallow rays on a transposed copy of the image.
 // Adjoint: gather, one thread per pixel: per angle the detectors whose rays can touch the pixel (its centre's projection +- the
@@ -704,14 +705,16 @@ __global__ __launch_bounds__(256) void k_fan_fwd(const float* __restrict__ img, 
   } else if (g.sy <= -half || g.sy >= half) t1 = -1.f;
   float acc = 0.f;
   if (t1 > t0) {
-    // first pixel: from the midpoint of a tiny first step
-    const float tm = t0 + 1e-4f * (t1 - t0);
-    int ix = (int)floorf(g.sx + tm * dx + half), iy = (int)floorf(g.sy + tm * dy + half);
+    // first pixel: the one holding the entry point, clamped into the image (the entry lies on its edge).  It was taken 1e-4 of the
+    // chord further in, and a boundary crossed before that gave the first pixel's length to the next one: up to 1e-4 of the chord,
+    // 6e-2 at 512^2 (test_gpu_fanbeam_accuracy).  Picked a rounding's width wrong, the traversal corrects itself by a zero-length step.
+    int ix = (int)floorf(g.sx + t0 * dx + half), iy = (int)floorf(g.sy + t0 * dy + half);
     ix = ix < 0 ? 0 : (ix > N - 1 ? N - 1 : ix);
     iy = iy < 0 ? 0 : (iy > N - 1 ? N - 1 : iy);
     const int stepx = dx > 0.f ? 1 : -1, stepy = dy > 0.f ? 1 : -1;
     const float inf = 3.0e38f;
-    const float dtx = fabsf(dx) > 1e-12f ? fabsf(1.0f / dx) : inf, dty = fabsf(dy) > 1e-12f ? fabsf(1.0f / dy) : inf;
+    // the parameter of the next column (row) boundary, from the boundary itself at every crossing: carried by repeated adds of
+    // 1 / |dx| it gathered one rounding per crossing, up to 2N of them (6e-2 of length at 512^2: test_gpu_fanbeam_accuracy)
     float tnx = fabsf(dx) > 1e-12f ? ((float)(ix + (stepx > 0 ? 1 : 0)) - half - g.sx) / dx : inf;
     float tny = fabsf(dy) > 1e-12f ? ((float)(iy + (stepy > 0 ? 1 : 0)) - half - g.sy) / dy : inf;
     float t = t0;
@@ -722,10 +725,10 @@ __global__ __launch_bounds__(256) void k_fan_fwd(const float* __restrict__ img, 
       if (tn >= t1) break;
       if (tnx <= tny) {
         ix += stepx;
-        tnx += dtx;
+        tnx = ((float)(ix + (stepx > 0 ? 1 : 0)) - half - g.sx) / dx;
       } else {
         iy += stepy;
-        tny += dty;
+        tny = ((float)(iy + (stepy > 0 ? 1 : 0)) - half - g.sy) / dy;
       }
       t = tn;
       if ((unsigned)ix >= (unsigned)N || (unsigned)iy >= (unsigned)N) break;
