@@ -58,12 +58,23 @@ const char* trk_last_error(void);      /* thread-local, never NULL */
 int trk_device_info(int* cu_count, int* wavefront, int64_t* lds_per_cu, int64_t* hbm_bytes);
 
 /* ---------------------------------------------------------------- operators ----------- */
-/* 2-D blur, reflective boundary.  Replaces scipy.ndimage.convolve(X.reshape(nx,ny), PSF,
- * mode='reflect') (forward) and the same with flipud(fliplr(PSF)) (the reference's "transpose"),
- * trips/test_problems/Deblurring2D.py:66-73.  psf_host: kh x kw row-major doubles on the HOST
- * (copied).  Rank-1 PSFs (every Deblurring2D.Gauss PSF, :48-64) take a separable LDS-tiled path.
- * A kh x 1 PSF on an nx x 1 image is the 1-D blur of Deblurring1D.py:56-62. */
+/* 2-D blur.  Replaces scipy.ndimage.convolve(X.reshape(nx,ny), PSF, mode=m) (forward) and the
+ * same with flipud(fliplr(PSF)) (the reference's "transpose"), trips/test_problems/Deblurring2D.py:66-73.
+ * psf_host: kh x kw row-major doubles on the HOST (copied).  Rank-1 PSFs (every Deblurring2D.Gauss
+ * PSF, :48-64) take a separable LDS-tiled path.  A kh x 1 PSF on an nx x 1 image is the 1-D blur of
+ * Deblurring1D.py:56-62, 93-102.
+ * trk_blur2d_create: mode='reflect'.  trk_blur2d_create_bc: `boundary` is one of TRK_BOUNDARY_*, the
+ * scipy.ndimage modes of the same names (constant: fill value 0), at any distance from the image.
+ * The "transpose" is the flipped-PSF convolution in the same mode, as in the reference: the exact
+ * adjoint for an odd symmetric PSF under reflect / constant / wrap, not otherwise.  The tiled
+ * small-image CGLS (trk_cgls_tiled_caps) serves reflect only. */
+#define TRK_BOUNDARY_REFLECT 0   /* half-sample symmetric: d c b a | a b c d | d c b a  */
+#define TRK_BOUNDARY_CONSTANT 1  /* zeros outside the image                               */
+#define TRK_BOUNDARY_NEAREST 2   /* the edge sample repeated: a a a a | a b c d | d d d d */
+#define TRK_BOUNDARY_MIRROR 3    /* whole-sample symmetric: d c b | a b c d | c b a      */
+#define TRK_BOUNDARY_WRAP 4      /* periodic: a b c d | a b c d | a b c d                 */
 int trk_blur2d_create(const double* psf_host, int kh, int kw, int nx, int ny, trk_op** out);
+int trk_blur2d_create_bc(const double* psf_host, int kh, int kw, int nx, int ny, int boundary, trk_op** out);
 
 /* Parallel-beam Radon transform, Joseph / linear-interpolation projector, matched adjoint.
  * Replaces astra.OpTomo over create_proj_geom('parallel', 1, N, theta) + 'linear' projector and
@@ -705,7 +716,7 @@ int trk_hess_tikhonov(double* H_dev, int ldh, double* G_dev, double* Minv_dev, i
 /* CGLS on SMALL blur problems in two launches per iteration (CGLS.py:56-80): a workgroup owns a 32 x 32 tile and recomputes
  * in LDS what it needs of its neighbours' halo (p = t + beta p and w = A p on tile + halo) instead of waiting for them at a
  * kernel boundary; same buffers, scalar layout and results (to fp32 rounding of the partial sums' order) as
- * trk_cgls_iterate_fused (w is never stored).  trk_cgls_tiled_caps: *can = 1 for separable PSFs up to 9 x 9 on images of at
+ * trk_cgls_iterate_fused (w is never stored).  trk_cgls_tiled_caps: *can = 1 for separable reflect-boundary PSFs up to 9 x 9 on images of at
  * least 16 x 16 whose tile count fits the norm-partial rows (np_capacity_blocks) and the PG / PD buffers (pcap). */
 int trk_cgls_tiled_caps(trk_op* A, int np_capacity_blocks, int pcap, int* can);
 int trk_cgls_iterate_tiled(trk_op* A, int k_first, int n_iters, float* P, int64_t p_ld, float* R, int64_t r_ld, float* t,

@@ -136,6 +136,7 @@ SIGNATURES = {
     "trk_last_error": (ctypes.c_char_p, []),
     "trk_device_info": (c_int, [ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
     "trk_blur2d_create": (c_int, [ctypes.POINTER(c_dbl), c_int, c_int, c_int, c_int, ctypes.POINTER(c_op)]),
+    "trk_blur2d_create_bc": (c_int, [ctypes.POINTER(c_dbl), c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_op)]),
     "trk_radon2d_create": (c_int, [c_int, c_int, ctypes.POINTER(c_dbl), c_int, c_dbl, ctypes.POINTER(c_op)]),
     "trk_radon2d_dynamic_create": (c_int, [c_int, c_int, ctypes.POINTER(c_dbl), c_int, c_int, c_dbl, ctypes.POINTER(c_op)]),
     "trk_fanbeam2d_create": (c_int, [c_int, c_int, c_dbl, c_dbl, c_dbl, ctypes.POINTER(c_dbl), c_int, ctypes.POINTER(c_op)]),

@@ -1,7 +1,7 @@
-// blur2d.hip — 2-D blur with reflective ('reflect' = half-sample symmetric) boundary for gfx950.
+// blur2d.hip — 2-D blur with scipy.ndimage's boundary modes for gfx950.
 //
-// Replaces scipy.ndimage.convolve(X.reshape(nx,ny), PSF, mode='reflect') and its flipped-PSF "transpose"
-// (trips/test_problems/Deblurring2D.py:66-73):
+// Replaces scipy.ndimage.convolve(X.reshape(nx,ny), PSF, mode=m) and its flipped-PSF "transpose"
+// (trips/test_problems/Deblurring2D.py:66-73; Deblurring1D.py:56-62, 93-102 for the 1-D form with any mode):
 //     y[i,j] = sum_{a,b} PSF[a,b] * xr[i + kh/2 - a, j + kw/2 - b]
 // written here as a correlation  y[i,j] = sum_{a',b'} c[a',b'] * xr[i - T + a', j - L + b'],
 //     c[a',b'] = PSF[kh-1-a', kw-1-b'],  T = kh-1-kh/2,  L = kw-1-kw/2.
@@ -18,7 +18,16 @@
 //     PSFs: the direct KH*KW form from the same 12 floats).  Stores are 16-byte coalesced.  Optionally sum(y^2) is
 //     accumulated per thread in fp64 over all steps and reduced once per workgroup (wave64 shuffles).
 //   * grid = strips x row bands, sized to ~4 workgroups per CU so that a 4096^2 image is split evenly (no tail).
-//   * k_blur_generic: any PSF size (even, rectangular, longer than the image: repeated reflection), no tiling.
+//   * k_blur_generic: any PSF size (even, rectangular, longer than the image: repeated extension), no tiling.
+//
+// Boundary modes (trk.h TRK_BOUNDARY_*): the index map of an out-of-image sample is a compile-time parameter BC of every
+// kernel (bmap<BC> below, valid at any distance from the image):
+//   reflect (half-sample symmetric, period 2n; the default)  constant (0)  nearest (clamp)  mirror (whole-sample, period
+//   2n-2)  wrap (period n).
+// Instantiated: every mode x every K of every kernel form — k_blur_slide plain / FUSE / EPI, k_blur_strip, k_blur_generic.
+// The reflect instantiations are the code that existed before the modes did (bmap<BC_REFLECT> == reflect()).  The "transpose"
+// is the flipped-PSF convolution in the same mode, as in the reference: the exact adjoint only for reflect / constant / wrap
+// with an odd symmetric PSF.
 #include "trk_internal.h"
 #include <hip/hip_ext.h>
 
@@ -48,8 +57,57 @@ __device__ __forceinline__ int reflect(int i, int n) {
   return (i >= n) ? (p - 1 - i) : i;
 }
 
+// boundary modes: the values of trk.h's TRK_BOUNDARY_*
+enum Bc : int { BC_REFLECT = 0, BC_CONSTANT = 1, BC_NEAREST = 2, BC_MIRROR = 3, BC_WRAP = 4 };
+
+// image index of sample i of a length-n line extended by mode BC, at any distance; -1 for a constant-mode sample outside
+// (the caller reads 0 there and forms no address)
+template <int BC>
+__device__ __forceinline__ int bmap(int i, int n) {
+  if constexpr (BC == BC_REFLECT) {
+    return reflect(i, n);
+  } else {
+    if ((unsigned)i < (unsigned)n) return i;
+    if constexpr (BC == BC_CONSTANT) {
+      return -1;
+    } else if constexpr (BC == BC_NEAREST) {
+      return i < 0 ? 0 : n - 1;
+    } else if constexpr (BC == BC_WRAP) {
+      i %= n;
+      return i < 0 ? i + n : i;
+    } else {   // BC_MIRROR: whole-sample symmetric, period 2n-2 (n = 1: the one sample)
+      if (n == 1) return 0;
+      const int p = 2 * n - 2;
+      i %= p;
+      if (i < 0) i += p;
+      return (i >= n) ? (p - i) : i;
+    }
+  }
+}
+
+// one sample of row `row` (length n) at column j under mode BC
+template <int BC>
+__device__ __forceinline__ float bload(const float* row, int j, int n) {
+  const int g = bmap<BC>(j, n);
+  if constexpr (BC == BC_CONSTANT)
+    if (g < 0) return 0.f;
+  return row[g];
+}
+
+template <class F>
+int bc_dispatch(int bc, F&& f) {   // run f with the mode as a compile-time constant
+  switch (bc) {
+    case BC_CONSTANT: return f(std::integral_constant<int, BC_CONSTANT>{});
+    case BC_NEAREST: return f(std::integral_constant<int, BC_NEAREST>{});
+    case BC_MIRROR: return f(std::integral_constant<int, BC_MIRROR>{});
+    case BC_WRAP: return f(std::integral_constant<int, BC_WRAP>{});
+    default: return f(std::integral_constant<int, BC_REFLECT>{});
+  }
+}
+
 struct BlurImpl {
   int nx, ny, kh, kw;
+  int bc;              // boundary mode (Bc)
   bool separable;
   bool tiled;          // a k_blur_strip instantiation exists for (kh,kw)
   float* w_dev[2];     // [kh*kw] correlation weights: 0 forward, 1 "transpose" (flipped PSF)
@@ -59,7 +117,7 @@ struct BlurImpl {
 // ------------------------------------------------------------------------------------------------ strip kernel
 // min waves per SIMD asked of the register allocator: 4 (= 4 workgroups per CU) for the separable kernels up to 9x9,
 // 2 for the register-hungry direct / large-PSF forms
-template <int KH, int KW, bool SEP, bool SUMSQ>
+template <int KH, int KW, bool SEP, bool SUMSQ, int BC = BC_REFLECT>
 __global__ __launch_bounds__(NT, (SEP && KH <= 9) ? 4 : 2) void k_blur_strip(const float* __restrict__ x, int64_t ldx, float* __restrict__ y,
                                                    int64_t ldy, int nx, int ny, const float* __restrict__ wts,
                                                    double* __restrict__ partials, int strips_x, int rows_per_band) {
@@ -85,17 +143,19 @@ __global__ __launch_bounds__(NT, (SEP && KH <= 9) ? 4 : 2) void k_blur_strip(con
   x += (int64_t)blockIdx.y * ldx;
   y += (int64_t)blockIdx.y * ldy;
 
-  // staged row `rel` is image row (i_begin - T + rel), reflected; it lives in ring slot rel % RING.
+  // staged row `rel` is image row (i_begin - T + rel), extended by mode BC; it lives in ring slot rel % RING.
   // With ny % 4 == 0 and an aligned base every 4-column group of a staged row is either wholly inside the image
-  // (one 16-byte load) or wholly outside (halo of the first / last strip: four reflected scalar loads).
+  // (one 16-byte load) or wholly outside (halo of the first / last strip: four extended scalar loads).
   const bool fast = ((ny & 3) == 0) && ((reinterpret_cast<uintptr_t>(x) & 15u) == 0);
 
   auto load_group = [&](int rel, int c4) -> f4 {   // 4 staged columns of staged row `rel`
-    const int gi = reflect(i_begin - T + rel, nx);
+    const int gi = bmap<BC>(i_begin - T + rel, nx);
+    if constexpr (BC == BC_CONSTANT)
+      if (gi < 0) return (f4){0.f, 0.f, 0.f, 0.f};    // a zero row: no address is formed
     const int gc = j0 - LP + 4 * c4;
     const float* row = x + (int64_t)gi * ny;
     if (fast && gc >= 0 && gc + 3 < ny) return *reinterpret_cast<const f4*>(row + gc);
-    return (f4){row[reflect(gc, ny)], row[reflect(gc + 1, ny)], row[reflect(gc + 2, ny)], row[reflect(gc + 3, ny)]};
+    return (f4){bload<BC>(row, gc, ny), bload<BC>(row, gc + 1, ny), bload<BC>(row, gc + 2, ny), bload<BC>(row, gc + 3, ny)};
   };
 
   auto load_direct = [&](int rel0, int count) {   // global -> LDS, rows rel0 .. rel0+count-1
@@ -273,7 +333,7 @@ struct SlideEpi {
   Coef a, b;
 };
 
-template <int KH, int KW, int D, bool SUMSQ, bool FUSE, bool EPI = false>
+template <int KH, int KW, int D, bool SUMSQ, bool FUSE, bool EPI = false, int BC = BC_REFLECT>
 __global__ __launch_bounds__(64) void k_blur_slide(const float* __restrict__ x, int64_t ldx, float* __restrict__ y,
                                                    int64_t ldy, int nx, int ny, const float* __restrict__ wts,
                                                    double* __restrict__ partials, int spans_x, int nbands,
@@ -304,8 +364,10 @@ __global__ __launch_bounds__(64) void k_blur_slide(const float* __restrict__ x, 
   const int c0 = span * SPAN + 4 * lane;
   const bool active = c0 < ny;
   const int cc = active ? c0 : ny - 4;                 // clamped: every load address is valid
-  const int cl = (cc >= 4) ? cc - 4 : 0;
-  const int cr = (cc + 8 <= ny) ? cc + 4 : ny - 4;
+  // the left / right neighbour groups; at the image's edges a valid in-image group that the border rule below replaces,
+  // except for wrap, whose edge lanes load the far end of the row (ny % 4 == 0 on this path: a whole group)
+  const int cl = (BC == BC_WRAP && c0 == 0) ? ny - 4 : (cc >= 4) ? cc - 4 : 0;
+  const int cr = (BC == BC_WRAP && c0 + 4 == ny) ? 0 : (cc + 8 <= ny) ? cc + 4 : ny - 4;
   const bool ledge = (c0 == 0), redge = (c0 + 4 == ny);
   const bool edge_span = (span == 0) || ((span + 1) * SPAN >= ny);   // wave-uniform
 
@@ -348,7 +410,15 @@ __global__ __launch_bounds__(64) void k_blur_slide(const float* __restrict__ x, 
   f4 qL[FUSE ? D : 1], qC[FUSE ? D : 1], qR[FUSE ? D : 1];
   auto issue = [&](int t, int slot) {
     int gi = first + dir * t;
-    if (!interior) gi = reflect(gi, nx);
+    if (!interior) gi = bmap<BC>(gi, nx);
+    if constexpr (BC == BC_CONSTANT) {
+      if (gi < 0) {                                    // a row outside the image (wave-uniform): zeros, no load issued
+        const f4 z = (f4){0.f, 0.f, 0.f, 0.f};
+        pL[slot] = pC[slot] = pR[slot] = z;
+        if (FUSE) qL[slot] = qC[slot] = qR[slot] = z;
+        return;
+      }
+    }
     const int so = gi * rowbytes;
     pL[slot] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(rin, vl, so, 0));
     pC[slot] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(rin, vc, so, 0));
@@ -402,10 +472,27 @@ __global__ __launch_bounds__(64) void k_blur_slide(const float* __restrict__ x, 
           __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, Cv), rcomb, vst + graw * rowbytes, 0, 0);
       }
       if (!GUARD || t + D < total) issue(t + D, slot);  // refill the slot D rows ahead
-      if (edge_span) {                                  // reflect across the image's left / right border
-        const f4 rev = (f4){Cv[3], Cv[2], Cv[1], Cv[0]};
-        if (ledge) Lv = rev;
-        if (redge) Rv = rev;
+      if constexpr (BC == BC_REFLECT) {
+        if (edge_span) {                                // reflect across the image's left / right border
+          const f4 rev = (f4){Cv[3], Cv[2], Cv[1], Cv[0]};
+          if (ledge) Lv = rev;
+          if (redge) Rv = rev;
+        }
+      } else if constexpr (BC != BC_WRAP) {             // (wrap: the edge lanes loaded the far end of the row)
+        if (edge_span) {
+          f4 le, re;
+          if constexpr (BC == BC_CONSTANT) {
+            le = re = (f4){0.f, 0.f, 0.f, 0.f};
+          } else if constexpr (BC == BC_NEAREST) {
+            le = (f4){Cv[0], Cv[0], Cv[0], Cv[0]};
+            re = (f4){Cv[3], Cv[3], Cv[3], Cv[3]};
+          } else {                                      // mirror: columns -4..-1 are 4..1, ny..ny+3 are ny-2..ny-5
+            le = (f4){Rv[0], Cv[3], Cv[2], Cv[1]};
+            re = (f4){Cv[2], Cv[1], Cv[0], Lv[3]};
+          }
+          if (ledge) Lv = le;
+          if (redge) Rv = re;
+        }
       }
       const float v[12] = {Lv[0], Lv[1], Lv[2], Lv[3], Cv[0], Cv[1], Cv[2], Cv[3], Rv[0], Rv[1], Rv[2], Rv[3]};
       float h0 = 0.f, h1 = 0.f, h2 = 0.f, h3 = 0.f;
@@ -479,7 +566,7 @@ __global__ __launch_bounds__(64) void k_blur_slide(const float* __restrict__ x, 
 }
 
 // ------------------------------------------------------------------------------------------------ generic kernel
-template <bool SUMSQ>
+template <bool SUMSQ, int BC = BC_REFLECT>
 __global__ __launch_bounds__(NT) void k_blur_generic(const float* __restrict__ x, int64_t ldx, float* __restrict__ y,
                                                      int64_t ldy, int nx, int ny, int kh, int kw,
                                                      const float* __restrict__ w, double* __restrict__ partials) {
@@ -493,9 +580,11 @@ __global__ __launch_bounds__(NT) void k_blur_generic(const float* __restrict__ x
     const int i = (int)(idx / ny), j = (int)(idx - (int64_t)i * ny);
     float acc = 0.f;
     for (int a = 0; a < kh; ++a) {
-      const int gi = reflect(i - T + a, nx);
+      const int gi = bmap<BC>(i - T + a, nx);
+      if constexpr (BC == BC_CONSTANT)
+        if (gi < 0) continue;                        // a zero row
       const float* row = x + (int64_t)gi * ny;
-      for (int b = 0; b < kw; ++b) acc = fmaf(w[a * kw + b], row[reflect(j - L + b, ny)], acc);
+      for (int b = 0; b < kw; ++b) acc = fmaf(w[a * kw + b], bload<BC>(row, j - L + b, ny), acc);
     }
     y[idx] = acc;
     if (SUMSQ) ss += (double)acc * acc;
@@ -519,13 +608,13 @@ inline void strip_grid(int nx, int ny, int batch, int* strips_x, int* rows_per_b
   *nband = ceil_div(nx, *rows_per_band);
 }
 
-template <int K>
+template <int K, int BC>
 int launch_strip(const BlurImpl* im, int tr, const float* x, int64_t ldx, float* y, int64_t ldy, int batch,
                  double* part, int strips_x, int rows_per_band, int nband, hipStream_t s) {
   dim3 grid(strips_x * nband, batch), block(NT);
   const float* w = im->separable ? im->sep_dev[tr] : im->w_dev[tr];
 #define BL(SEP, SS) \
-  hipLaunchKernelGGL((k_blur_strip<K, K, SEP, SS>), grid, block, 0, s, x, ldx, y, ldy, im->nx, im->ny, w, part, strips_x, rows_per_band)
+  hipLaunchKernelGGL((k_blur_strip<K, K, SEP, SS, BC>), grid, block, 0, s, x, ldx, y, ldy, im->nx, im->ny, w, part, strips_x, rows_per_band)
   if (im->separable) { if (part) BL(true, true); else BL(true, false); }
   else               { if (part) BL(false, true); else BL(false, false); }
 #undef BL
@@ -533,7 +622,7 @@ int launch_strip(const BlurImpl* im, int tr, const float* x, int64_t ldx, float*
   return TRK_OK;
 }
 
-template <int K, int D>
+template <int K, int D, int BC>
 int launch_slide(const BlurImpl* im, int tr, const float* x, int64_t ldx, float* y, int64_t ldy, int batch,
                  double* part, int spans_x, int nbands, int rows_per_band, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1,
                  const SlideFuse* fuse = nullptr, const SlideEpi* epi = nullptr) {
@@ -541,25 +630,25 @@ int launch_slide(const BlurImpl* im, int tr, const float* x, int64_t ldx, float*
   const float* w = im->sep_dev[tr];
   const int nts = stream_nontemporal((int64_t)im->nx * im->ny);
   if (fuse) {   // fused-operand form: always with the sum of squares (raw partials)
-    hipExtLaunchKernelGGL((k_blur_slide<K, K, D, true, true>), grid, block, 0, s, ev0, ev1, 0, x, ldx, y, ldy, im->nx, im->ny, w, part, spans_x, nbands, rows_per_band, *fuse, nts, SlideEpi{});
+    hipExtLaunchKernelGGL((k_blur_slide<K, K, D, true, true, false, BC>), grid, block, 0, s, ev0, ev1, 0, x, ldx, y, ldy, im->nx, im->ny, w, part, spans_x, nbands, rows_per_band, *fuse, nts, SlideEpi{});
     TRK_LAUNCH_CHECK();
     return TRK_OK;
   }
   const SlideFuse nofuse{nullptr, nullptr, 0.0, {nullptr, 0}, {nullptr, 0}};
   if (epi) {
     if (part)
-      hipExtLaunchKernelGGL((k_blur_slide<K, K, D, true, false, true>), grid, block, 0, s, ev0, ev1, 0, x, ldx, y, ldy, im->nx, im->ny, w, part, spans_x, nbands, rows_per_band, nofuse, nts, *epi);
+      hipExtLaunchKernelGGL((k_blur_slide<K, K, D, true, false, true, BC>), grid, block, 0, s, ev0, ev1, 0, x, ldx, y, ldy, im->nx, im->ny, w, part, spans_x, nbands, rows_per_band, nofuse, nts, *epi);
     else
-      hipExtLaunchKernelGGL((k_blur_slide<K, K, D, false, false, true>), grid, block, 0, s, ev0, ev1, 0, x, ldx, y, ldy, im->nx, im->ny, w, part, spans_x, nbands, rows_per_band, nofuse, nts, *epi);
+      hipExtLaunchKernelGGL((k_blur_slide<K, K, D, false, false, true, BC>), grid, block, 0, s, ev0, ev1, 0, x, ldx, y, ldy, im->nx, im->ny, w, part, spans_x, nbands, rows_per_band, nofuse, nts, *epi);
     TRK_LAUNCH_CHECK();
     return TRK_OK;
   }
   // hipExtLaunchKernelGGL attaches the (optional) events to the dispatch itself: their timestamps are the kernel's own
   // begin / end, the same quantity rocprofv3's kernel trace reports.
   if (part)
-    hipExtLaunchKernelGGL((k_blur_slide<K, K, D, true, false>), grid, block, 0, s, ev0, ev1, 0, x, ldx, y, ldy, im->nx, im->ny, w, part, spans_x, nbands, rows_per_band, nofuse, nts, SlideEpi{});
+    hipExtLaunchKernelGGL((k_blur_slide<K, K, D, true, false, false, BC>), grid, block, 0, s, ev0, ev1, 0, x, ldx, y, ldy, im->nx, im->ny, w, part, spans_x, nbands, rows_per_band, nofuse, nts, SlideEpi{});
   else
-    hipExtLaunchKernelGGL((k_blur_slide<K, K, D, false, false>), grid, block, 0, s, ev0, ev1, 0, x, ldx, y, ldy, im->nx, im->ny, w, part, spans_x, nbands, rows_per_band, nofuse, nts, SlideEpi{});
+    hipExtLaunchKernelGGL((k_blur_slide<K, K, D, false, false, false, BC>), grid, block, 0, s, ev0, ev1, 0, x, ldx, y, ldy, im->nx, im->ny, w, part, spans_x, nbands, rows_per_band, nofuse, nts, SlideEpi{});
   TRK_LAUNCH_CHECK();
   return TRK_OK;
 }
@@ -633,13 +722,16 @@ int blur_apply_fused(trk_op* op, int tr, const float* x1, const float* x2, doubl
       ev1 = t->ev[2 * t->used + 1];
       ++t->used;
     }
-  switch (im->kh) {
-    case 3: return launch_slide<3, 6>(im, tr, x1, 0, y, 0, 1, partials, spans_x, nbands, rpb, s, ev0, ev1, fzp);
-    case 5: return launch_slide<5, 5>(im, tr, x1, 0, y, 0, 1, partials, spans_x, nbands, rpb, s, ev0, ev1, fzp);
-    case 7: return launch_slide<7, 7>(im, tr, x1, 0, y, 0, 1, partials, spans_x, nbands, rpb, s, ev0, ev1, fzp);
-    default:
-      return launch_slide<9, 9>(im, tr, x1, 0, y, 0, 1, partials, spans_x, nbands, rpb, s, ev0, ev1, fzp);
-  }
+  return bc_dispatch(im->bc, [&](auto bc) {
+    constexpr int BC = decltype(bc)::value;
+    switch (im->kh) {
+      case 3: return launch_slide<3, 6, BC>(im, tr, x1, 0, y, 0, 1, partials, spans_x, nbands, rpb, s, ev0, ev1, fzp);
+      case 5: return launch_slide<5, 5, BC>(im, tr, x1, 0, y, 0, 1, partials, spans_x, nbands, rpb, s, ev0, ev1, fzp);
+      case 7: return launch_slide<7, 7, BC>(im, tr, x1, 0, y, 0, 1, partials, spans_x, nbands, rpb, s, ev0, ev1, fzp);
+      default:
+        return launch_slide<9, 9, BC>(im, tr, x1, 0, y, 0, 1, partials, spans_x, nbands, rpb, s, ev0, ev1, fzp);
+    }
+  });
 }
 
 int blur_apply(trk_op* op, int tr, const float* x, int64_t ldx, float* y, int64_t ldy, int batch, double* sumsq,
@@ -663,15 +755,15 @@ int blur_apply(trk_op* op, int tr, const float* x, int64_t ldx, float* y, int64_
         ev1 = t->ev[2 * t->used + 1];
         ++t->used;
       }
-    int rc;
-    switch (im->kh) {
-      case 3: rc = launch_slide<3, 6>(im, tr, x, ldx, y, ldy, batch, part, spans_x, nbands, rpb, s, ev0, ev1); break;
-      case 5: rc = launch_slide<5, 5>(im, tr, x, ldx, y, ldy, batch, part, spans_x, nbands, rpb, s, ev0, ev1); break;
-      case 7: rc = launch_slide<7, 7>(im, tr, x, ldx, y, ldy, batch, part, spans_x, nbands, rpb, s, ev0, ev1); break;
-      default:
-        rc = launch_slide<9, 9>(im, tr, x, ldx, y, ldy, batch, part, spans_x, nbands, rpb, s, ev0, ev1);
-        break;
-    }
+    const int rc = bc_dispatch(im->bc, [&](auto bc) {
+      constexpr int BC = decltype(bc)::value;
+      switch (im->kh) {
+        case 3: return launch_slide<3, 6, BC>(im, tr, x, ldx, y, ldy, batch, part, spans_x, nbands, rpb, s, ev0, ev1);
+        case 5: return launch_slide<5, 5, BC>(im, tr, x, ldx, y, ldy, batch, part, spans_x, nbands, rpb, s, ev0, ev1);
+        case 7: return launch_slide<7, 7, BC>(im, tr, x, ldx, y, ldy, batch, part, spans_x, nbands, rpb, s, ev0, ev1);
+        default: return launch_slide<9, 9, BC>(im, tr, x, ldx, y, ldy, batch, part, spans_x, nbands, rpb, s, ev0, ev1);
+      }
+    });
     if (rc) return rc;
     if (sumsq) return finalize_sums(part, nblk * batch, 1, 1, sumsq, s);
     return TRK_OK;
@@ -683,17 +775,19 @@ int blur_apply(trk_op* op, int tr, const float* x, int64_t ldx, float* y, int64_
     if (sumsq)
       if (int rc = scratch_doubles(s, (size_t)nblk * batch, &part)) return rc;
     TimerScope tm(op->timer, op->timer_which, tr, s);
-    int rc;
-    switch (im->kh) {
-      case 3: rc = launch_strip<3>(im, tr, x, ldx, y, ldy, batch, part, strips_x, rows_per_band, nband, s); break;
-      case 5: rc = launch_strip<5>(im, tr, x, ldx, y, ldy, batch, part, strips_x, rows_per_band, nband, s); break;
-      case 7: rc = launch_strip<7>(im, tr, x, ldx, y, ldy, batch, part, strips_x, rows_per_band, nband, s); break;
-      case 9: rc = launch_strip<9>(im, tr, x, ldx, y, ldy, batch, part, strips_x, rows_per_band, nband, s); break;
-      case 11: rc = launch_strip<11>(im, tr, x, ldx, y, ldy, batch, part, strips_x, rows_per_band, nband, s); break;
-      case 13: rc = launch_strip<13>(im, tr, x, ldx, y, ldy, batch, part, strips_x, rows_per_band, nband, s); break;
-      case 15: rc = launch_strip<15>(im, tr, x, ldx, y, ldy, batch, part, strips_x, rows_per_band, nband, s); break;
-      default: return fail(TRK_EUNSUPPORTED, "blur2d: no strip kernel for %dx%d", im->kh, im->kw);
-    }
+    const int rc = bc_dispatch(im->bc, [&](auto bc) {
+      constexpr int BC = decltype(bc)::value;
+      switch (im->kh) {
+        case 3: return launch_strip<3, BC>(im, tr, x, ldx, y, ldy, batch, part, strips_x, rows_per_band, nband, s);
+        case 5: return launch_strip<5, BC>(im, tr, x, ldx, y, ldy, batch, part, strips_x, rows_per_band, nband, s);
+        case 7: return launch_strip<7, BC>(im, tr, x, ldx, y, ldy, batch, part, strips_x, rows_per_band, nband, s);
+        case 9: return launch_strip<9, BC>(im, tr, x, ldx, y, ldy, batch, part, strips_x, rows_per_band, nband, s);
+        case 11: return launch_strip<11, BC>(im, tr, x, ldx, y, ldy, batch, part, strips_x, rows_per_band, nband, s);
+        case 13: return launch_strip<13, BC>(im, tr, x, ldx, y, ldy, batch, part, strips_x, rows_per_band, nband, s);
+        case 15: return launch_strip<15, BC>(im, tr, x, ldx, y, ldy, batch, part, strips_x, rows_per_band, nband, s);
+        default: return fail(TRK_EUNSUPPORTED, "blur2d: no strip kernel for %dx%d", im->kh, im->kw);
+      }
+    });
     tm.stop();
     if (rc) return rc;
   } else {
@@ -705,10 +799,14 @@ int blur_apply(trk_op* op, int tr, const float* x, int64_t ldx, float* y, int64_
       if (int rc = scratch_doubles(s, (size_t)nblk * batch, &part)) return rc;
     dim3 grid(nblk, batch);
     TimerScope tm(op->timer, op->timer_which, tr, s);
-    if (part)
-      hipLaunchKernelGGL((k_blur_generic<true>), grid, dim3(NT), 0, s, x, ldx, y, ldy, im->nx, im->ny, im->kh, im->kw, im->w_dev[tr], part);
-    else
-      hipLaunchKernelGGL((k_blur_generic<false>), grid, dim3(NT), 0, s, x, ldx, y, ldy, im->nx, im->ny, im->kh, im->kw, im->w_dev[tr], part);
+    bc_dispatch(im->bc, [&](auto bc) {
+      constexpr int BC = decltype(bc)::value;
+      if (part)
+        hipLaunchKernelGGL((k_blur_generic<true, BC>), grid, dim3(NT), 0, s, x, ldx, y, ldy, im->nx, im->ny, im->kh, im->kw, im->w_dev[tr], part);
+      else
+        hipLaunchKernelGGL((k_blur_generic<false, BC>), grid, dim3(NT), 0, s, x, ldx, y, ldy, im->nx, im->ny, im->kh, im->kw, im->w_dev[tr], part);
+      return 0;
+    });
     tm.stop();
     TRK_LAUNCH_CHECK();
   }
@@ -736,13 +834,15 @@ int blur_apply_axpby_plain(trk_op* op, int tr, const float* x, Coef a, Coef b, c
       ++t->used;
     }
   const SlideEpi ep{z, a, b};
-  int rc;
-  switch (im->kh) {
-    case 3: rc = launch_slide<3, 6>(im, tr, x, 0, out, 0, 1, part, spans_x, nbands, rpb, s, ev0, ev1, nullptr, &ep); break;
-    case 5: rc = launch_slide<5, 5>(im, tr, x, 0, out, 0, 1, part, spans_x, nbands, rpb, s, ev0, ev1, nullptr, &ep); break;
-    case 7: rc = launch_slide<7, 7>(im, tr, x, 0, out, 0, 1, part, spans_x, nbands, rpb, s, ev0, ev1, nullptr, &ep); break;
-    default: rc = launch_slide<9, 9>(im, tr, x, 0, out, 0, 1, part, spans_x, nbands, rpb, s, ev0, ev1, nullptr, &ep); break;
-  }
+  const int rc = bc_dispatch(im->bc, [&](auto bc) {
+    constexpr int BC = decltype(bc)::value;
+    switch (im->kh) {
+      case 3: return launch_slide<3, 6, BC>(im, tr, x, 0, out, 0, 1, part, spans_x, nbands, rpb, s, ev0, ev1, nullptr, &ep);
+      case 5: return launch_slide<5, 5, BC>(im, tr, x, 0, out, 0, 1, part, spans_x, nbands, rpb, s, ev0, ev1, nullptr, &ep);
+      case 7: return launch_slide<7, 7, BC>(im, tr, x, 0, out, 0, 1, part, spans_x, nbands, rpb, s, ev0, ev1, nullptr, &ep);
+      default: return launch_slide<9, 9, BC>(im, tr, x, 0, out, 0, 1, part, spans_x, nbands, rpb, s, ev0, ev1, nullptr, &ep);
+    }
+  });
   if (rc) return rc;
   if (sumsq) return finalize_sums(part, nblk, 1, 1, sumsq, s);
   return TRK_OK;
@@ -759,12 +859,15 @@ void blur_destroy(trk_op* op) {
 
 }  // namespace
 
-// what the tiled small-image CGLS (cgls_tiled.hip) needs of a blur handle: sizes and the separable weights on the device
+// what the tiled small-image CGLS (cgls_tiled.hip) needs of a blur handle: sizes, the separable weights on the device and the
+// boundary mode (TRK_BOUNDARY_*)
 namespace trk {
-bool blur_separable_params(trk_op* op, int* nx, int* ny, int* kh, int* kw, const float** sep_fwd, const float** sep_adj) {
+bool blur_separable_params(trk_op* op, int* nx, int* ny, int* kh, int* kw, const float** sep_fwd, const float** sep_adj,
+                           int* boundary) {
   if (!op || op->kind != 1) return false;
   auto* im = static_cast<BlurImpl*>(op->impl);
   if (!im->separable || !im->sep_dev[0] || !im->sep_dev[1]) return false;
+  if (boundary) *boundary = im->bc;
   *nx = im->nx;
   *ny = im->ny;
   *kh = im->kh;
@@ -776,10 +879,18 @@ bool blur_separable_params(trk_op* op, int* nx, int* ny, int* kh, int* kw, const
 }  // namespace trk
 
 extern "C" int trk_blur2d_create(const double* psf, int kh, int kw, int nx, int ny, trk_op** out) {
+  return trk_blur2d_create_bc(psf, kh, kw, nx, ny, TRK_BOUNDARY_REFLECT, out);
+}
+
+extern "C" int trk_blur2d_create_bc(const double* psf, int kh, int kw, int nx, int ny, int boundary, trk_op** out) {
   TRK_REQUIRE(psf && out, "trk_blur2d_create: NULL argument");
   TRK_REQUIRE(kh >= 1 && kw >= 1 && nx >= 1 && ny >= 1, "trk_blur2d_create: sizes must be >= 1");
   TRK_REQUIRE((int64_t)kh * kw <= (1 << 24), "trk_blur2d_create: PSF too large");
-  auto* im = new BlurImpl{nx, ny, kh, kw, false, false, {nullptr, nullptr}, {nullptr, nullptr}};
+  TRK_REQUIRE(boundary >= TRK_BOUNDARY_REFLECT && boundary <= TRK_BOUNDARY_WRAP, "trk_blur2d_create_bc: unknown boundary mode %d", boundary);
+  static_assert(TRK_BOUNDARY_REFLECT == BC_REFLECT && TRK_BOUNDARY_CONSTANT == BC_CONSTANT && TRK_BOUNDARY_NEAREST == BC_NEAREST &&
+                    TRK_BOUNDARY_MIRROR == BC_MIRROR && TRK_BOUNDARY_WRAP == BC_WRAP,
+                "blur2d boundary modes follow trk.h");
+  auto* im = new BlurImpl{nx, ny, kh, kw, boundary, false, false, {nullptr, nullptr}, {nullptr, nullptr}};
 
   // correlation weights: forward c[a'][b'] = psf[kh-1-a'][kw-1-b'];  "transpose" convolves with flip(psf): c = psf
   std::vector<float> wf((size_t)kh * kw), wt((size_t)kh * kw);

@@ -510,10 +510,11 @@ __global__ __launch_bounds__(NT) void k_cgls_tile_b2(TiledGeom g, const float* _
 }
 
 int tiled_geom(trk_op* A, TiledGeom* g, int* ntiles) {
-  int nx, ny, kh, kw;
+  int nx, ny, kh, kw, bc;
   const float *sf, *st;
-  if (!blur_separable_params(A, &nx, &ny, &kh, &kw, &sf, &st)) return 0;
-  if (kh > 9 || kw > 9 || nx < 16 || ny < 16) return 0;
+  if (!blur_separable_params(A, &nx, &ny, &kh, &kw, &sf, &st, &bc)) return 0;
+  // the tiles' halo rule is the reflective one: a blur with another boundary mode takes the streaming loop
+  if (bc != TRK_BOUNDARY_REFLECT || kh > 9 || kw > 9 || nx < 16 || ny < 16) return 0;
   float hf[18], ht[18];
   if (hipMemcpy(hf, sf, sizeof(float) * (kw + kh), hipMemcpyDeviceToHost) != hipSuccess ||
       hipMemcpy(ht, st, sizeof(float) * (kw + kh), hipMemcpyDeviceToHost) != hipSuccess) {
@@ -582,7 +583,7 @@ int trk_cgls_iterate_tiled(trk_op* A, int k_first, int n_iters, float* P, int64_
   TRK_REQUIRE(k_first >= 1 && n_iters >= 0, "trk_cgls_iterate_tiled: need k_first >= 1, n_iters >= 0");
   const TiledCache* tc = tiled_cache(A);
   if (!tc) return TRK_EHIP;                                // (message set by tiled_cache)
-  if (tc->ntiles <= 0) return fail(TRK_EUNSUPPORTED, "trk_cgls_iterate_tiled: needs a separable blur <= 9x9 on an image >= 16x16");
+  if (tc->ntiles <= 0) return fail(TRK_EUNSUPPORTED, "trk_cgls_iterate_tiled: needs a reflect-boundary separable blur <= 9x9 on an image >= 16x16");
   const TiledGeom g = tc->g;
   const int ntiles = tc->ntiles;
   TRK_REQUIRE(ntiles <= np_capacity_blocks && ntiles <= pcap, "trk_cgls_iterate_tiled: %d tiles exceed the partial buffers", ntiles);
@@ -622,7 +623,7 @@ int trk_cgls_iterate_tiled2(trk_op* A, int k_first, int n_iters, float* p, float
   TRK_REQUIRE(k_first >= 1 && n_iters >= 0, "trk_cgls_iterate_tiled2: need k_first >= 1, n_iters >= 0");
   const TiledCache* tc = tiled_cache(A);
   if (!tc) return TRK_EHIP;
-  if (tc->ntiles <= 0) return fail(TRK_EUNSUPPORTED, "trk_cgls_iterate_tiled2: needs a separable blur <= 9x9 on an image >= 16x16");
+  if (tc->ntiles <= 0) return fail(TRK_EUNSUPPORTED, "trk_cgls_iterate_tiled2: needs a reflect-boundary separable blur <= 9x9 on an image >= 16x16");
   const TiledGeom g = tc->g;
   const int ntiles = tc->ntiles;
   TRK_REQUIRE(ntiles <= np_capacity_blocks && ntiles <= pcap, "trk_cgls_iterate_tiled2: %d tiles exceed the partial buffers", ntiles);

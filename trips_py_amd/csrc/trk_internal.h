@@ -388,8 +388,10 @@ int scale_by_partials(int64_t n, const double* part, int nblk, const float* x, f
                       hipStream_t s, const float* dotv = nullptr, double* dot_out = nullptr);   // dotv: also *dot_out = <out, dotv>, posted with the rest
 // projected.hip: finalize of the 2k sums of gemv_t2_partials and trk_cgs_coeffs(G, ldg, W, W + k, k, passes, c) in one launch
 int finalize_cgs(const double* part, int nblk, int k, double* W, double* G, int ldg, int passes, double* c, hipStream_t s);
-// blur2d.hip: sizes and device pointers to the separable weights [kw row weights | kh column weights] of a blur handle
-bool blur_separable_params(trk_op* op, int* nx, int* ny, int* kh, int* kw, const float** sep_fwd, const float** sep_adj);
+// blur2d.hip: sizes, device pointers to the separable weights [kw row weights | kh column weights] and the boundary mode
+// (TRK_BOUNDARY_*) of a blur handle
+bool blur_separable_params(trk_op* op, int* nx, int* ny, int* kh, int* kw, const float** sep_fwd, const float** sep_adj,
+                           int* boundary);
 }  // namespace trk
 
 // One step of damped LSQR's short recurrence (trk_lsqr_damped_update) as a rider on another kernel's pixel pass: the vector vk of

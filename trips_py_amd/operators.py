@@ -197,10 +197,35 @@ def _dbl_array(a):
     return a, a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
 
 
-class Blur2D(_HandleOperator):
-    """y = scipy.ndimage.convolve(x.reshape(nx,ny), psf, mode='reflect'); `.T` = the same with the flipped PSF."""
+# scipy.ndimage boundary modes the blur serves, by their trk.h codes (TRK_BOUNDARY_*), and scipy's aliases of them
+BOUNDARY_MODES = {"reflect": 0, "constant": 1, "nearest": 2, "mirror": 3, "wrap": 4}
+_BOUNDARY_ALIASES = {"grid-mirror": "reflect", "grid-constant": "constant", "grid-wrap": "wrap"}
 
-    def __init__(self, psf, nx, ny, engine=None):
+
+def normalize_boundary(mode, cval=0.0):
+    """The canonical name of a scipy.ndimage boundary mode for the blur ('grid-*' aliases resolved).  Raises ValueError for
+    a mode the blur does not serve and for a non-zero fill value (constant mode pads with 0 only)."""
+    if not isinstance(mode, str):
+        raise ValueError(f"boundary mode must be a string, got {mode!r}")
+    name = _BOUNDARY_ALIASES.get(mode, mode)
+    if name not in BOUNDARY_MODES:
+        raise ValueError(f"unknown boundary mode {mode!r}: expected one of {sorted(BOUNDARY_MODES) + sorted(_BOUNDARY_ALIASES)}")
+    if cval != 0:
+        raise ValueError(f"only the fill value 0 is supported (got cval={cval!r})")
+    return name
+
+
+class Blur2D(_HandleOperator):
+    """y = scipy.ndimage.convolve(x.reshape(nx,ny), psf, mode=boundary); `.T` = the same with the flipped PSF, in the same
+    mode (the reference's "transpose", Deblurring2D.py:70-71, Deblurring1D.py:59-62).
+
+    boundary: 'reflect' (default), 'constant' (zero fill), 'nearest', 'mirror', 'wrap', or scipy's aliases 'grid-mirror',
+    'grid-constant', 'grid-wrap'; `self.boundary` holds the canonical name.  The flipped-PSF "transpose" is the exact adjoint
+    only for an odd-sized point-symmetric PSF under 'reflect', 'constant' or 'wrap'.  Under 'nearest' / 'mirror', or with an
+    even-sized PSF in any mode, it differs from A^T in entries next to the border, as the reference's does."""
+
+    def __init__(self, psf, nx, ny, engine=None, boundary="reflect"):
+        self.boundary = normalize_boundary(boundary)       # (a bad name fails before any device is touched)
         engine = engine if engine is not None else default_engine()
         psf = np.asarray(psf, dtype=np.float64)
         if psf.ndim != 2:
@@ -208,18 +233,20 @@ class Blur2D(_HandleOperator):
         self.psf, self.nx, self.ny = psf, int(nx), int(ny)
         arr, p = _dbl_array(psf)
         h = ctypes.c_void_p()
-        _lib.check(engine.lib.trk_blur2d_create(p, psf.shape[0], psf.shape[1], self.nx, self.ny, ctypes.byref(h)), "trk_blur2d_create")
+        _lib.check(engine.lib.trk_blur2d_create_bc(p, psf.shape[0], psf.shape[1], self.nx, self.ny, BOUNDARY_MODES[self.boundary],
+                                                   ctypes.byref(h)), "trk_blur2d_create_bc")
         super().__init__(h, engine)
         self.streaming = max(psf.shape) <= 15          # the sliding-window / LDS-strip kernels (csrc/blur2d.hip)
 
 
 class Blur1D(Blur2D):
-    """1-D blur with a (possibly length-n) PSF: an n x 1 image and a k x 1 PSF."""
+    """1-D blur with a (possibly length-n) PSF: an n x 1 image and a k x 1 PSF; scipy.ndimage.convolve1d(x, psf, mode=boundary)
+    (modes and the "transpose" as Blur2D)."""
 
-    def __init__(self, psf, n=None, engine=None):
+    def __init__(self, psf, n=None, engine=None, boundary="reflect"):
         psf = np.asarray(psf, dtype=np.float64).reshape(-1)
         n = len(psf) if n is None else int(n)
-        super().__init__(psf.reshape(-1, 1), n, 1, engine)
+        super().__init__(psf.reshape(-1, 1), n, 1, engine, boundary=boundary)
 
 
 class Radon2DParallel(_HandleOperator):

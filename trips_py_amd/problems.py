@@ -12,7 +12,7 @@ holds it as mixins (`demo_classes()`), for a notebook that wants the reference's
 """
 import numpy as np
 
-from .operators import Blur1D, Blur2D, BlockDiagOp, FanBeam2D, Radon2DParallel
+from .operators import Blur1D, Blur2D, BlockDiagOp, FanBeam2D, Radon2DParallel, normalize_boundary
 
 
 def gauss_psf(dim, spread):
@@ -48,10 +48,11 @@ class Deblurring2D:
         self.dim, self.spread = PSFdim, PSFspread
         return gauss_psf(PSFdim, PSFspread)
 
-    def forward_Op(self, dim, spread, nx, ny, engine=None):
+    def forward_Op(self, dim, spread, nx, ny, engine=None, boundary_condition="reflect"):
+        """boundary_condition (an extension: the reference's 2-D blur is always 'reflect'): any mode Blur2D accepts."""
         self.nx, self.ny = nx, ny
         psf, _ = self.Gauss(dim, spread)
-        return Blur2D(psf, nx, ny, engine=engine)
+        return Blur2D(psf, nx, ny, engine=engine, boundary=boundary_condition)
 
 
 class Deblurring1D:
@@ -68,11 +69,13 @@ class Deblurring1D:
         return psf, int(np.where(psf == psf.max())[0][0])
 
     def forward_Op_1D(self, parameter, nx, boundary_condition="reflect", engine=None):
-        if boundary_condition != "reflect":
-            raise NotImplementedError("only the 'reflect' boundary is implemented on the engine")
+        """boundary_condition: the scipy.ndimage mode of the forward convolve1d and of the flipped-PSF "transpose" (:56-62) —
+        'reflect', 'constant' (0), 'nearest', 'mirror', 'wrap' or a 'grid-*' alias of them; stored as given, as the reference
+        does.  The "transpose" is not the exact adjoint for 'nearest' / 'mirror' (nor, in any mode, for an even n)."""
+        normalize_boundary(boundary_condition)
         self.parameter, self.boundary_condition = parameter, boundary_condition
         self.PSF, self.center = self.Gauss1D(nx, parameter)
-        return Blur1D(self.PSF, nx, engine=engine)
+        return Blur1D(self.PSF, nx, engine=engine, boundary=boundary_condition)
 
 
 class Tomography:
