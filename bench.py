@@ -1,8 +1,13 @@
 #!/usr/bin/env python
-"""bench.py — Krylov iterations/second on the 4096 x 4096 blur, with the blur-matvec HBM roofline and a same-box
-CPU baseline, as one JSON line (driver contract).
+"""bench.py — Krylov iterations/second on the 4096 x 4096 blur, with the blur-matvec HBM roofline, as one JSON line
+(driver contract).
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: set-up, run-in, warm-up, the K timed steps, --dump-outputs if given, and the
+line (with the forward-blur roofline read from events recorded inside the timed steps).  `--full` adds everything else,
+after the timed steps: the adjoint-kernel timing, the communicator checks, the secondary configurations
+under "extra" (C2-C5, hybrid solvers, fan-beam, sparse), whole-solve rates and the same-box CPU baselines.
 
 N > 1: one rank per GPU.  Either a launcher started the ranks (`python -m torch.distributed.run --nproc-per-node N ...
 bench.py --gpus N`: RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment), or — plain `python bench.py --gpus N`
@@ -12,9 +17,9 @@ A "step" is one Krylov iteration of the workload's solver on one batch of synthe
 resident in HBM before the timed region).  Static single-image problems do not shard (replicas only):
 with N ranks every rank solves its own 4096^2 problem and `value` is the aggregate iterations/s ("weak").
 The sharded dynamic-tomography configuration (frames over ranks, RCCL all-reduce of the inner products) is measured
-in the same run and reported under "extra" (it is not `value`).
+in the same `--full` run and reported under "extra" (it is not `value`).
 
-Only the `cpu_baseline` leg touches oracle/ (the float64 NumPy/SciPy restatement of the reference path, calling
+Only the `cpu_baseline` legs (`--full`) touch oracle/ (the float64 NumPy/SciPy restatement of the reference path, calling
 scipy.ndimage.convolve exactly as Deblurring2D.py:70-71 does) — as the reported baseline, never as the thing measured.
 """
 import argparse
@@ -60,11 +65,15 @@ def parse():
                          "the per-iteration CGLS scalars) as DIR/<name>.npy")
     ap.add_argument("--size", type=int, default=4096, help="image side of the blur workload")
     ap.add_argument("--workload", default="blur_cgls", choices=["blur_cgls"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything that is not the headline: adjoint-kernel timing, "
+                         "communicator checks, the secondary configurations, whole-solve rates and the CPU baselines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--unfused", action="store_true", help="force the generic (unfused-operand) CGLS iteration")
     ap.add_argument("--fused", action="store_true", help="force the fused three-launch CGLS iteration")
-    ap.add_argument("--no-extras", action="store_true", help="skip the C4 (MMGKS) and C5 (sharded dynamic tomo) legs")
-    ap.add_argument("--cpu-iters", type=int, default=8, help="CPU-baseline sample: CGLS iterations timed on the host")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the secondary configurations and the whole-solve rates")
+    ap.add_argument("--cpu-iters", type=int, default=8, help="CPU-baseline sample (--full): CGLS iterations timed on the host")
     ap.add_argument("--run-in", type=int, default=RUN_IN_ITERS,
                     help="untimed iterations of the same loop BEFORE the --warmup ones (clock / cache settling; stated in the line)")
     return ap.parse_args()
@@ -288,16 +297,6 @@ def run_blur_cgls(args, rank, world, json_fd=1):
     _g0, rows = run.rows()
     assert np.all(np.isfinite(rows)) and rows.shape[0] == W + K
 
-    # transpose kernel, timed the same way in a short extra loop (outside the timed region)
-    tadj = KernelTimer(A, 32, 1)
-    tadj.attach()
-    y = eng.empty(n)
-    for _ in range(20):
-        A.apply(b, out=y, transpose=True)
-    torch.cuda.synchronize()
-    tadj.detach()
-    ms_adj = tadj.read()
-
     # algorithmic bytes of the forward-blur launch: plain matvec reads x and writes y (8 n); the fused form also reads
     # p_old and writes p_new (16 n) — SURVEY §8d's own accounting of a fused update + matvec
     alg_bytes = (16.0 if fused else 8.0) * n
@@ -316,9 +315,24 @@ def run_blur_cgls(args, rank, world, json_fd=1):
                 "min_kernel_us": round(float(np.min(ms_fwd)) * 1e3, 2),
                 "median_kernel_us": round(float(np.median(ms_fwd)) * 1e3, 2),
                 "p90_kernel_us": round(float(np.percentile(ms_fwd, 90)) * 1e3, 2),
-                "max_kernel_us": round(float(np.max(ms_fwd)) * 1e3, 2), "launches_timed": int(len(ms_fwd)),
-                "adjoint_matvec_avg_kernel_us": round(float(np.mean(ms_adj[2:])) * 1e3, 2),
-                "adjoint_matvec_GBps": round(8.0 * n / (float(np.mean(ms_adj[2:])) * 1e-3) / 1e9, 1)}
+                "max_kernel_us": round(float(np.max(ms_fwd)) * 1e3, 2), "launches_timed": int(len(ms_fwd))}
+    extra = {}
+    if args.full:
+        # transpose kernel, timed the same way in a short extra loop (outside the timed region)
+        tadj = KernelTimer(A, 32, 1)
+        tadj.attach()
+        y = eng.empty(n)
+        for _ in range(20):
+            A.apply(b, out=y, transpose=True)
+        torch.cuda.synchronize()
+        tadj.detach()
+        ms_adj = tadj.read()
+        roofline["adjoint_matvec_avg_kernel_us"] = round(float(np.mean(ms_adj[2:])) * 1e3, 2)
+        roofline["adjoint_matvec_GBps"] = round(8.0 * n / (float(np.mean(ms_adj[2:])) * 1e-3) / 1e9, 1)
+        extra["comm"] = comm_check(rank, world)
+        extra["relError_after_timed_iters"] = float(torch.linalg.norm(run.x_cur - x_true) / torch.linalg.norm(x_true))
+    extra["cgls_alg_bytes_per_iter"] = 44.0 * n
+    extra["cgls_effective_GBps"] = round(44.0 * n * K / elapsed / 1e9, 1)
 
     res = {"metric": "krylov_iters_per_sec", "value": round(world * K / elapsed, 3), "unit": "iters/s",
            "n_gpus": world, "steps": K, "warmup": W, "run_in_iters": RI, "ms_per_step": round(elapsed / K * 1e3, 4),
@@ -333,12 +347,9 @@ def run_blur_cgls(args, rank, world, json_fd=1):
                                     if getattr(run, "raw", False) else "generic: 6 launches"),
                       "parallelism": (f"replicas: `value` is {world} independent {N}x{N} solves, one per GPU, no collective on the data path "
                                       "(a static single-image problem does not shard: DESIGN.md 5) — the SHARDED workload of north_star "
-                                      "(C5, frames over ranks, RCCL all-reduce per iteration) is the top-level `sharded` object") if world > 1 else "single"},
+                                      "(C5, frames over ranks, RCCL all-reduce per iteration) is the top-level `sharded` object (with --full)") if world > 1 else "single"},
            "roofline": roofline,
-           "extra": {"comm": comm_check(rank, world),
-                     "relError_after_timed_iters": float(torch.linalg.norm(run.x_cur - x_true) / torch.linalg.norm(x_true)),
-                     "cgls_alg_bytes_per_iter": 44.0 * n,
-                     "cgls_effective_GBps": round(44.0 * n * K / elapsed / 1e9, 1)}}
+           "extra": extra}
 
     def solves_leg():
         """solver rates "history off and on", and what a reference-style call sees from idle.  Whole CGLS() calls of
@@ -378,14 +389,14 @@ def run_blur_cgls(args, rank, world, json_fd=1):
     # solver loop enqueueing microsecond kernels stops for ~100 ms (seen here as C4 at 170 instead of 540
     # iterations/s when the C3 host leg ran right before it).
     cpu_jobs = []          # (where the result goes, closure)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         b_host = b.detach().to("cpu")
         cpu_jobs.append((lambda v: res.__setitem__("cpu_baseline", v), lambda: cpu_baseline_cgls(psf, N, b_host, args.cpu_iters)))
     if args.dump_outputs:
         dump_outputs(args.dump_outputs, rank, world, run.x_cur, rows)
     del run
     torch.cuda.empty_cache()
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         # secondary measurements (never `value`): each guarded so that the main line is always printed — against
         # exceptions by try/except, against a hang (e.g. one rank failing inside a collective) by a watchdog that prints
         # the line with whatever is measured so far and ends the process
@@ -1201,7 +1212,7 @@ def main():
     if not torch.cuda.is_available():
         print("bench.py needs a GPU (the engine has no CPU fallback)", file=sys.stderr)
         sys.exit(2)
-    if int(os.environ.get("WORLD_SIZE", "1")) == 1:
+    if args.full and int(os.environ.get("WORLD_SIZE", "1")) == 1:
         os.environ.setdefault("TRK_COMM_FORCE", "1")      # the RCCL latency probe of extra.trk_comm_rccl on one rank (see its note)
     rank, world = dist_setup(args)
     res = run_blur_cgls(args, rank, world, json_fd)

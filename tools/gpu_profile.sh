@@ -5,7 +5,7 @@ O=$R/gpurun_out/profile_r01
 mkdir -p $O
 export TMPDIR=/tmp
 cd $R
-python bench.py --steps 100 --warmup 10 > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; cat $O/bench.json
+timeout -k 10 900 python bench.py --steps 100 --warmup 10 --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; cat $O/bench.json
 cd /tmp
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 $R/bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-extras > $O/trace_bench.json 2> $O/trace.err; echo "trace rc=$?"
 timeout 600 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $O/pmc_fetch -- python3 $R/bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras > /dev/null 2>&1; echo "pmc1 rc=$?"

@@ -14,9 +14,9 @@ test)
 smoke)
   timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke rc=$?"; tail -2 $O/smoke.log ;;
 bench)
-  timeout 900 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; cat $O/bench.json ;;
+  timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; cat $O/bench.json ;;
 bench2)
-  TRK_DIST_BACKEND=gloo TRK_SINGLE_DEVICE=1 timeout 900 python bench.py --gpus 2 --steps 50 --no-cpu-baseline > $O/bench_2ranks_gloo.json 2> $O/bench2.err; echo "bench2 rc=$?"; cat $O/bench_2ranks_gloo.json; tail -3 $O/bench2.err ;;
+  TRK_DIST_BACKEND=gloo TRK_SINGLE_DEVICE=1 timeout 900 python bench.py --gpus 2 --steps 50 --full --no-cpu-baseline > $O/bench_2ranks_gloo.json 2> $O/bench2.err; echo "bench2 rc=$?"; cat $O/bench_2ranks_gloo.json; tail -3 $O/bench2.err ;;
 prof)
   for c in c3 c4 c5; do
     (cd /tmp && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$c -- python3 $R/tools/configs_micro.py $c > $O/prof_$c.log 2>&1); echo "prof $c rc=$?"
