@@ -2,7 +2,7 @@
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
-if os.environ.get("TRK_EXPERIMENT_LIB"):          # a library built with experiment macros (tools/r05_band_exp.sh): timing only
+if os.environ.get("TRK_EXPERIMENT_LIB"):          # another build of the library (A/B timing)
     from trips_py_amd import _lib as _L
     _L.LIB_PATH = os.environ["TRK_EXPERIMENT_LIB"]
     _L._stale = lambda: False

@@ -340,8 +340,8 @@ def load():
     path = LIB_PATH
     exp = os.environ.get("TRK_EXPERIMENT_LIB")
     if exp:
-        # A/B measurements of kernel variants on ONE box (tools/r06_ab_libs.sh builds them with -DTRK_... switches): a library of the same
-        # ABI under another path.  Announced on stderr; never set by the product.
+        # A/B measurements on ONE box (a library built from another revision of the sources, e.g. the parent commit): a library of the
+        # same ABI under another path.  Announced on stderr; never set by the product.
         if not os.path.exists(exp):
             raise TrkError(f"TRK_EXPERIMENT_LIB={exp}: no such file")
         print(f"trips_py_amd: loading the EXPERIMENT library {exp} instead of {LIB_PATH}", file=sys.stderr)

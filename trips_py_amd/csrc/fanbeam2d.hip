@@ -792,16 +792,14 @@ int fan_apply(trk_op* op, int tr, const float* x, int64_t ldx, float* y, int64_t
               hipStream_t s) {
   auto* im = static_cast<FanImpl*>(op->impl);
   TimerScope tm(op->timer, op->timer_which, tr, s);
-  static const bool siddon = getenv("TRK_FAN_SIDDON") != nullptr;       // the general pair, for comparison
-  const bool march = im->rays && !siddon;
+  const bool march = im->rays != nullptr;
   if (!tr && march) {
     const int nb = ceil_div(im->N, 32);
     const int64_t padded = (int64_t)im->N * (im->N + 2 * FAN_PAD);
     const int64_t nrays = (int64_t)im->na * im->nd;
     // bands of the march: enough waves to hide the gathers (about 8 per SIMD), at most the 4 floats per ray that the adjoint's
     // record array (unused during a forward apply) has room for, bands of at least 64 steps and a multiple of 8
-    static const int fb_env = getenv("TRK_FAN_FWD_BANDS") ? atoi(getenv("TRK_FAN_FWD_BANDS")) : 0;
-    int nbands = fb_env > 0 ? fb_env : (int)((8 * 4 * (int64_t)cu_count() * 64 + nrays - 1) / nrays);
+    int nbands = (int)((8 * 4 * (int64_t)cu_count() * 64 + nrays - 1) / nrays);
     if (nbands > 4) nbands = 4;
     if (nbands > im->N / 64) nbands = im->N / 64;
     if (nbands < 1) nbands = 1;

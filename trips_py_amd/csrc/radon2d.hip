@@ -1319,11 +1319,7 @@ __global__ __launch_bounds__(256, 4) void k_radon_fwd_quadf(const float* __restr
 // as k_radon_fwd_lds sums them; the band partials go to the same array (64-row bands).  Grid: frames x {row bands, column bands} x
 // slices of that mode's angle list (adj_ang: the angles sorted by mode), about one workgroup per CU.
 constexpr int BR_ROWS = 64, BR_NW = 16, BR_NT = 64 * BR_NW, BR_PAD = 4, BR_NMAX = 1024;
-#ifdef TRK_FWD_EXPERIMENT_FLUSH16                      // (A/B build switch: rounds 2-5's fp32 sums of 16 rows)
-constexpr int BR_FLUSH_SHIFT = 4;
-#else
 constexpr int BR_FLUSH_SHIFT = 2;                      // fp32 sums of 4 rows, then float64
-#endif
 // rows per band: 64 where 64 x (N + 8) floats fit (N <= 512), else 32 (N <= 1024: 132 KB)
 inline int br_rows(int N) { return (size_t)BR_ROWS * (N + 2 * BR_PAD) * 4 <= 150 * 1024 ? BR_ROWS : BR_ROWS / 2; }
 __global__ __launch_bounds__(BR_NT, 4) void k_radon_fwd_band(const float* __restrict__ img, const float* __restrict__ imgT,
@@ -1347,23 +1343,10 @@ __global__ __launch_bounds__(BR_NT, 4) void k_radon_fwd_band(const float* __rest
   const int cnt = mode ? na - n0 : n0;                           // angles of this mode in the frame
   const int ndblk = (nd + 63) / 64;
   // the mode's (angle, 64 detectors) tasks in list order, dealt to the slices in equal contiguous shares
-#ifdef TRK_BAND_EXPERIMENT_PAIR
-  // TIMING EXPERIMENT ONLY (wrong results): every second angle of the mode's list, each task also summing a MIRRORED ray with the same
-  // weights (what a pair of symmetric angles sharing one march would cost)
-  const int all_tasks = (cnt / 2) * ndblk;
-#else
   const int all_tasks = cnt * ndblk;
-#endif
   const int task0 = (int)((int64_t)all_tasks * slice / nslice), task1 = (int)((int64_t)all_tasks * (slice + 1) / nslice);
   if (task1 <= task0) return;
   const int RS = N + 2 * BR_PAD;                                 // row stride in floats (a multiple of 4)
-#ifdef TRK_RADON_BAND_EXPERIMENT
-  // timing experiments only (tools/r05_band_exp.sh builds a separate library; results are wrong with either bit): have_xT & 2 = the
-  // band load alone, & 4 = the march alone (over whatever the LDS holds)
-  const bool x_loadonly = (have_xT & 2) != 0, x_noload = (have_xT & 4) != 0;
-  have_xT &= 1;
-  if (!x_noload)
-#endif
   if (mode && !have_xT) {
     // no transposed copy at hand: the band of the transposed image is 64 COLUMNS of the image — a wave-load takes 16 image rows x 16
     // columns (whole 64-byte sectors), a lane's four values go to four rows of the band (consecutive lanes: consecutive addresses)
@@ -1416,12 +1399,6 @@ __global__ __launch_bounds__(BR_NT, 4) void k_radon_fwd_band(const float* __rest
   }
   if (threadIdx.x == 0) next_task = task0 + nw;
   __syncthreads();
-#ifdef TRK_RADON_BAND_EXPERIMENT
-  if (x_loadonly) {
-    if (threadIdx.x == 0) part[blockIdx.x] = band[blockIdx.x & 1023];
-    return;
-  }
-#endif
   float two32 = 4294967296.0f;
   asm("" : "+s"(two32));
   const int t0 = b * rows;
@@ -1433,12 +1410,7 @@ __global__ __launch_bounds__(BR_NT, 4) void k_radon_fwd_band(const float* __rest
   // two chunks of its first task: 21.9 us.  Nor the row stride as a compile-time constant with the row offsets as immediates of two hand-issued
   // ds_read_b32 per step (no scalar instruction per step: 80 -> 45 per chunk, twice the LDS instructions): 27.3 us per plain apply against 26.2.)
   for (int task = task0 + wv; task < task1;) {
-#ifdef TRK_BAND_EXPERIMENT_PAIR
-    const int ai = 2 * (task / ndblk), dblk = task - (ai / 2) * ndblk;
-    double total_m = 0.0;
-#else
     const int ai = task / ndblk, dblk = task - ai * ndblk;
-#endif
     const int a = frame * na + sorted[frame * na + (mode ? n0 : 0) + ai].orig;                    // (scalar loads)
     const AngleParam p = ang[a];
     const int nlive = (nd - dblk * 64 < 64) ? nd - dblk * 64 : 64;
@@ -1464,15 +1436,9 @@ __global__ __launch_bounds__(BR_NT, 4) void k_radon_fwd_band(const float* __rest
       // showed what the longer fp32 chains cost where the solver amplifies roundings — iterates 5-7 of C3's transient sat 44-90 x
       // above the fp32-storage floor with 16-row sums and on it with 4-row sums (R.set_ref_sums(4, 32))
       f2v acc2[4] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
-#ifdef TRK_BAND_EXPERIMENT_PAIR
-      f2v acc2m[4] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
-#endif
       if (cs >= 0 && ce <= N - 1) {
         // every tap of the wave inside the image: address = row (scalar) + 4 (cs + pad) (scalar) + 4 * relative column
         f2v w[16], t2[16];
-#ifdef TRK_BAND_EXPERIMENT_PAIR
-        f2v t2m[16];
-#endif
 #pragma unroll
         for (int u = 0; u < 16; ++u) {
           const unsigned Q = Ac + Brow[u];
@@ -1483,19 +1449,9 @@ __global__ __launch_bounds__(BR_NT, 4) void k_radon_fwd_band(const float* __rest
           asm("" : "+s"(off));
           const float* tp = reinterpret_cast<const float*>(rowp + off + ((Q >> QF) << 2));
           t2[u] = (f2v){tp[0], tp[1]};
-#ifdef TRK_BAND_EXPERIMENT_PAIR
-          int offm = u * RS * 4 + (BR_PAD + N - 2 - cs) * 4;
-          asm("" : "+s"(offm));
-          const float* tpm = reinterpret_cast<const float*>(rowp + offm - ((Q >> QF) << 2));
-          t2m[u] = (f2v){tpm[0], tpm[1]};
-#endif
         }
 #pragma unroll
         for (int u = 0; u < 16; ++u) acc2[u >> BR_FLUSH_SHIFT] = __builtin_elementwise_fma(w[u], t2[u], acc2[u >> BR_FLUSH_SHIFT]);
-#ifdef TRK_BAND_EXPERIMENT_PAIR
-#pragma unroll
-        for (int u = 0; u < 16; ++u) asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,0,0] op_sel_hi:[0,1,1]" : "+v"(acc2m[u >> BR_FLUSH_SHIFT]) : "v"(w[u]), "v"(t2m[u]));
-#endif
       } else {
         // the window overhangs the image: columns clamped into the zero pads ([-2, N]: both taps of a clamped step read zeros)
         f2v w[16], t2[16];
@@ -1517,15 +1473,8 @@ __global__ __launch_bounds__(BR_NT, 4) void k_radon_fwd_band(const float* __rest
       }
 #pragma unroll
       for (int g4 = 0; g4 < 4; ++g4) total += (double)(acc2[g4][0] + acc2[g4][1]);
-#ifdef TRK_BAND_EXPERIMENT_PAIR
-#pragma unroll
-      for (int g4 = 0; g4 < 4; ++g4) total_m += (double)(acc2m[g4][0] + acc2m[g4][1]);
-#endif
     }
     if (live) part[(int64_t)b * band_stride + (int64_t)a * nd + d] = (float)total;
-#ifdef TRK_BAND_EXPERIMENT_PAIR
-    if (live && ai + 1 < cnt) part[(int64_t)b * band_stride + (int64_t)(frame * na + sorted[frame * na + (mode ? n0 : 0) + ai + 1].orig) * nd + d] = (float)total_m;
-#endif
     int nx = 0;
     if (lane == 0) nx = atomicAdd(&next_task, 1);
     task = __builtin_amdgcn_readfirstlane(nx);
@@ -1954,28 +1903,6 @@ __global__ __launch_bounds__(256 * G) void k_radon_adj_tile(const float* __restr
       }
       // (round 6) the NEXT angle's constants and {C, B32} pair are requested right behind this angle's record reads, so that one wait
       // covers both: angle by angle the loop had two exposed round trips (scalar + LDS for the pair, then LDS for the records)
-#ifdef TRK_ADJ_EXPERIMENT_NO_PIPELINE                 // (A/B build switch: rounds 2-5's loop, two waits per angle)
-#pragma unroll 2
-      for (; al < al_hi; ++al) {
-        const AdjAngle p = ang[a0 + al];
-        f2v cr = {p.c1m, p.c1p};
-        asm("" : "+s"(cr));
-        const uint2 cb = cbs[buf][al][cbrow];
-        const float C = __builtin_bit_cast(float, cb.x);
-        u4r rr[PX];
-#pragma unroll
-        for (int k = 0; k < PX; ++k) {
-          const unsigned bits = __builtin_bit_cast(unsigned, fmaf(fcol[k], p.rinv, C) + RND_MAGIC);
-          rr[k] = ring_read(rbase0 + al * 1024, bits);
-        }
-        ring_wait();
-#pragma unroll
-        for (int k = 0; k < PX; ++k) {
-          ring_tie(rr[k]);
-          adj_gather(rr[k], cb.y, ncol[k], sc2, nsc, cr, an[k], ac[k]);
-        }
-      }
-#else
       if (al < al_hi) {
         float pn_c1 = ang[a0 + al].c1m, pn_c1p = ang[a0 + al].c1p, pn_rinv = ang[a0 + al].rinv;     // wave-uniform: scalar loads
         u2r cbn = pair_read(&cbs[buf][al][cbrow]);
@@ -2009,11 +1936,9 @@ __global__ __launch_bounds__(256 * G) void k_radon_adj_tile(const float* __restr
           }
         }
       }
-#endif
     };
     angles(0, nm0, fcolA, colA, r0, anA, accA);
     angles(nm0, nal, fcolB, colB, c1, anB, accB);
-#ifndef TRK_ADJ_EXPERIMENT_NO_F64_TOTALS             // (A/B build switch: tools/r06_ab_libs.sh)
     if (((b + 1) * AB) % ADJ_FLUSH == 0) {           // wave-uniform; only the batch where the modes change flushes both
       if (nm0 > 0) {
 #pragma unroll
@@ -2032,7 +1957,6 @@ __global__ __launch_bounds__(256 * G) void k_radon_adj_tile(const float* __restr
         }
       }
     }
-#endif
     if (b + 1 < nbatch) stage_store(b + 1);          // the other buffer: nobody reads it before the next barrier
   }
   // the two partial images meet: mode-0 sums go through LDS to the thread that holds the pixel in the mode-1 layout
@@ -2285,13 +2209,6 @@ __global__ __launch_bounds__(256, 3) void k_radon_adj_quad(const uint4* __restri
   aq += (int64_t)frame * nq;
   CBq += (int64_t)frame * nq * npad;
   recq += (int64_t)frame * nq * 4 * ndp;
-#ifdef TRK_ADJQ_EXPERIMENT_SPLIT
-  {  // TIMING EXPERIMENT ONLY (wrong results: the splits overwrite each other): blockIdx.z takes a share of the quads
-    const int per = (nq + (int)gridDim.z - 1) / (int)gridDim.z, qs = blockIdx.z * per;
-    aq += qs; CBq += (int64_t)qs * npad; recq += (int64_t)qs * 4 * ndp;
-    nq = nq - qs < per ? (nq - qs < 0 ? 0 : nq - qs) : per;
-  }
-#endif
   const auto rrec = __builtin_amdgcn_make_buffer_rsrc((void*)recq, 0, (unsigned)((int64_t)nq * 4 * ndp * 16), 0x00020000);
   const auto rcb = __builtin_amdgcn_make_buffer_rsrc((void*)CBq, 0, (unsigned)((int64_t)nq * npad * 8), 0x00020000);
   const float sdh = 0.5f * (float)(nd - 1);
@@ -2561,30 +2478,79 @@ __global__ __launch_bounds__(256) void k_radon_adj_simple(const uint4* __restric
   }
 }
 
-// Which forward kernel an input at `xb` gets: per-wave LDS windows (N % 4 == 0, 16-byte aligned input; DMA = staged by direct-to-LDS
+// Which forward kernel an input at `xb` gets: per-wave LDS windows (N % 4 == 0, 16-byte aligned input; staged by direct-to-LDS
 // loads), the window-sharing kernel from 1024^2 on, else direct gathers.  direct1: the per-wave-window kernel reads the angles
 // marched along columns from the image itself, transposing while it stages — no transposed copy, no launch for it (512^2 x 180:
 // the copy was 5 of the apply's 31 us; 32 frames of 256^2: 5.8 of 23).  The window-sharing kernel keeps the copy (2.6 % at 4096^2).
+// (Global -> LDS directly, buffer_load_dwordx4 ... lds, new on gfx950, instead of through registers: 1.30 -> 1.11 ms at 4096^2.)
 struct FwdPath {
-  bool lds, dma, win, direct1, quad;
+  bool lds, win, direct1, quad;
 };
 FwdPath fwd_path(const RadonImpl* im, const float* xb) {
-  static const bool no_lds = getenv("TRK_RADON_NO_LDS") != nullptr;
-  // global -> LDS directly (buffer_load_dwordx4 ... lds, new on gfx950) instead of through registers: 1.30 -> 1.11 ms at 4096^2
-  static const bool dma = getenv("TRK_RADON_NO_DMA") == nullptr;
-  static const bool no_win = getenv("TRK_RADON_NO_WIN") != nullptr;
-  static const bool no_direct1 = getenv("TRK_RADON_NO_DIRECT1") != nullptr;
   FwdPath f;
-  f.lds = !no_lds && (im->N % 4 == 0) && ((reinterpret_cast<uintptr_t>(xb) & 15u) == 0);
-  f.dma = dma;
+  f.lds = (im->N % 4 == 0) && ((reinterpret_cast<uintptr_t>(xb) & 15u) == 0);
   // measured: 512^2 35 us (shared) vs 32 us (per-wave windows); 2048^2 0.256 vs 0.277 ms; 4096^2 0.96 vs 1.11 ms
-  static const int win_min = getenv("TRK_RADON_WIN_MIN") ? atoi(getenv("TRK_RADON_WIN_MIN")) : 1024;     // tuning knob
-  f.win = im->n_bands > 1 && im->N >= win_min && f.lds && dma && !no_win && im->band <= WIN_R * WIN_MAXCH && !im->band_res;
-  f.direct1 = f.lds && !f.win && !no_direct1;
+  f.win = im->n_bands > 1 && im->N >= 1024 && f.lds && im->band <= WIN_R * WIN_MAXCH && !im->band_res;
+  f.direct1 = f.lds && !f.win;
   // four symmetric angles per wave, conflict-free half-wave windows (k_radon_fwd_quad): 4096^2 x 180 0.94 -> see DESIGN.md 4.4
-  static const bool no_quad = getenv("TRK_RADON_NO_QUAD") != nullptr;
-  f.quad = f.win && !no_quad && im->nq > 0 && im->band <= QD_R * QD_MAXCH;
+  f.quad = f.win && im->nq > 0 && im->band <= QD_R * QD_MAXCH;
   return f;
+}
+
+// Which adjoint kernel a call gets.  `riders`: the fused epilogue carries the damped-LSQR update or the mailbox post.
+//   quad    k_radon_adj_quad by mirrored tile pairs, with its own pre-pass (k_radon_adj_prepq)
+//   groups  k_radon_adj_tile<32, 4, 8, *, 4>: the four parts of a split tile in one workgroup
+//   tileT*  k_radon_adj_tile<T, PX, AB, *>, split over `nsplit` workgroups per tile
+//   simple  k_radon_adj_simple, one pixel per thread (TRK_RADON_ADJ_SIMPLE=1, read per call: the tests switch it; frames below 16^2)
+// prep: the records come from k_radon_adj_prep (which a hinted forward may have run already), not from the tile kernel itself.
+// blocks: workgroups per frame and split part, one fused-norm partial each.
+enum class AdjKind { quad, groups, tile32_b8, tile16_b16, tile16_b4, simple };
+struct AdjPath {
+  AdjKind kind;
+  bool prep;
+  int nsplit, tiles_x;
+  int64_t blocks;
+};
+AdjPath adj_path(const RadonImpl* im, int batch, bool riders) {
+  const int N = im->N, na = im->na, nt = im->nt;
+  if (getenv("TRK_RADON_ADJ_SIMPLE") != nullptr || N < 16) return AdjPath{AdjKind::simple, true, 1, 0, ceil_div((int64_t)N * N, 256)};
+  AdjPath a{AdjKind::tile32_b8, na > 32, 1, 0, 0};     // few angles per frame: the tile kernel makes its records itself
+  // 32 x 32 tiles with 4 pixels per thread (fewest instructions per pixel) need enough tiles to fill the chip (frames of a
+  // dynamic problem count); below that 16 x 16 tiles with one pixel per thread (4 x the waves)
+  // measured: 512^2 x 180 (one frame: 256 / 1024 tiles) 51 vs 42 us; 32 frames x 256^2 x 15 (2048 / 8192 tiles) 21 vs 34 us
+  const int64_t tiles32 = (int64_t)ceil_div(N, 32) * ceil_div(N, 32) * nt;
+  // Too few 32 x 32 tiles to fill the chip, many angles: the angles of a tile are SPLIT over nsplit workgroups whose partial tiles
+  // meet in the one that finishes last (k_radon_adj_tile) — the instructions per pixel and angle of the 32 x 32 form (10.25 against
+  // 14.5 for 16 x 16 tiles with one pixel per thread, where the staging of a batch is shared by a quarter of the pixels) at the
+  // same number of waves.
+  // measured (us per apply, 180 angles; 16 x 16 tiles -> split 2 / 4 / 8): 256^2 24.1 -> 32.6 / 21.4 / 16.3, 512^2 32.9 -> 36.5 / 29.8 /
+  // 29.8, 768^2 63.2 -> 54.8 / 50.4 / 50.9; 1024^2 (1024 tiles: 32 x 32 unsplit already) 83 with or without
+  if (batch == 1 && tiles32 < 1024 && na > 32 && N >= 64) a.nsplit = tiles32 <= 128 ? 8 : 4;
+  const int T = (tiles32 >= 1024 || a.nsplit > 1) ? 32 : 16;
+  a.tiles_x = ceil_div(N, T);
+  a.blocks = (int64_t)a.tiles_x * a.tiles_x;
+  const int64_t wgs = a.blocks * nt;
+  if (T == 32) {
+    // round 6: the adjoint by mirrored tile pairs where the handle allows it (whole 64 x 64 super-tiles, mostly complete quads) and
+    // no rider travels on the epilogue (the damped-LSQR update and the mailbox post stay with k_radon_adj_tile);
+    // TRK_RADON_NO_ADJQ=1: k_radon_adj_tile everywhere (read per call: the tests switch it)
+    if (a.nsplit == 1 && im->adjq_ok && !riders && getenv("TRK_RADON_NO_ADJQ") == nullptr) {
+      a.kind = AdjKind::quad;
+      a.prep = true;
+      a.blocks = (int64_t)(N / 64) * (N / 64);
+    } else if (a.nsplit == 4 && wgs <= cu_count() && wgs * 4 >= 3 * cu_count()) {
+      a.kind = AdjKind::groups;    // the parts of a tile as groups of ONE workgroup where that gives about one workgroup per CU (512^2: 256 tiles)
+    }
+    // (16 angles per batch — half the barriers, twice the rings — measured at 512^2 x 180: 34.7 us against 29.9; and one batch for a
+    //  15-angle frame, measured again in round 6 on C5's shape, 32 frames of 256^2 x 15 angles: see profiles/r06/adj_ab16.txt)
+  } else if (na > 32 || wgs <= 4 * (int64_t)cu_count()) {
+    // 16 angles per batch also for the few frames of a dynamic problem one rank of eight holds — 4 frames of 256^2 x 15 angles, 1 024
+    // workgroups: 10.2 -> 9.1 us per apply, profiles/r06/adj_ab16.txt; with more workgroups than that the shorter batches win
+    a.kind = AdjKind::tile16_b16;
+  } else {
+    a.kind = AdjKind::tile16_b4;   // few angles per frame (dynamic problems: 15): short batches, so that staging and gathering still overlap
+  }
+  return a;
 }
 
 constexpr int HINT_OUT_FEEDS_OPPOSITE = 1, HINT_INPUT_FROM_OPPOSITE = 2, HINT_SUMSQ_DEFERRED = 4;   // = TRK_HINT_* (trk.h)
@@ -2622,51 +2588,19 @@ int radon_run(trk_op* op, int tr, const float* x, int64_t ldx, float* y, int64_t
       return rc;
     }
   }
+  const AdjPath ap = adj_path(im, batch, epi.on && (op->post.on || op->lsqr.on));
+  const bool tile = ap.kind != AdjKind::simple;
+  const int ndp = nd + 2 * A32_PAD;
   // fused ||y||^2 (batch 1): block partials from the kernel that writes y (band reduction / gather), then one finalize —
   // or none, when the caller lets the next chained apply finish it (TRK_HINT_SUMSQ_DEFERRED)
   double* ssq_part = nullptr;
-  const bool adj_simple = getenv("TRK_RADON_ADJ_SIMPLE") != nullptr;   // read per call: tests switch it
-  const bool tile = !adj_simple && N >= 16;
-  // 32 x 32 tiles with 4 pixels per thread (fewest instructions per pixel) need enough tiles to fill the chip (frames of a
-  // dynamic problem count); below that 16 x 16 tiles with one pixel per thread (4 x the waves)
-  static const int tile_env = getenv("TRK_RADON_ADJ_TILE") ? atoi(getenv("TRK_RADON_ADJ_TILE")) : 0;
-  // measured: 512^2 x 180 (one frame: 256 / 1024 tiles) 51 vs 42 us; 32 frames x 256^2 x 15 (2048 / 8192 tiles) 21 vs 34 us
-  const int64_t tiles32 = (int64_t)ceil_div(N, 32) * ceil_div(N, 32) * nt;
-  // Too few 32 x 32 tiles to fill the chip, many angles: the angles of a tile are SPLIT over nsplit workgroups whose partial tiles
-  // meet in the one that finishes last (k_radon_adj_tile) — the instructions per pixel and angle of the 32 x 32 form (10.25 against
-  // 14.5 for 16 x 16 tiles with one pixel per thread, where the staging of a batch is shared by a quarter of the pixels) at the
-  // same number of waves.  TRK_RADON_ADJ_SPLIT: 1 = off, 2 / 4 / 8 forces.
-  static const int split_env = getenv("TRK_RADON_ADJ_SPLIT") ? atoi(getenv("TRK_RADON_ADJ_SPLIT")) : 0;
-  int nsplit = 1;
-  // measured (us per apply, 180 angles; 16 x 16 tiles -> split 2 / 4 / 8): 256^2 24.1 -> 32.6 / 21.4 / 16.3, 512^2 32.9 -> 36.5 / 29.8 /
-  // 29.8, 768^2 63.2 -> 54.8 / 50.4 / 50.9; 1024^2 (1024 tiles: 32 x 32 unsplit already) 83 with or without
-  if (tile && !tile_env && batch == 1 && tiles32 < (split_env > 1 ? 4096 : 1024) && na > 32 && N >= 64) {
-    nsplit = split_env ? split_env : (tiles32 <= 128 ? 8 : 4);
-    nsplit = nsplit >= 8 ? 8 : (nsplit >= 4 ? 4 : (nsplit >= 2 ? 2 : 1));
-  }
-  const int tile_T = tile_env ? tile_env : ((tiles32 >= 1024 || nsplit > 1) ? 32 : 16);
-  static const int ab_env = getenv("TRK_RADON_ADJ_AB") ? atoi(getenv("TRK_RADON_ADJ_AB")) : 0;
-  const int tiles_x = ceil_div(N, tile_T);
-  const int64_t adj_blocks = tile ? (int64_t)tiles_x * tiles_x : (int64_t)ceil_div((int64_t)N * N, 256);
-  const int ndp = nd + 2 * A32_PAD;
-  const bool adj_prep = !tile || na > 32;            // few angles per frame: the tile kernel makes its records itself
-  // round 6: the adjoint by mirrored tile pairs (k_radon_adj_quad) where the handle allows it (whole 64 x 64 super-tiles, mostly
-  // complete quads) and no rider travels on the epilogue (the damped-LSQR update and the mailbox post stay with k_radon_adj_tile);
-  // TRK_RADON_NO_ADJQ=1: k_radon_adj_tile everywhere (read per call: the tests switch it)
-  const bool adjq_riders = epi.on && (op->post.on || op->lsqr.on);
-#ifdef TRK_ADJQ_EXPERIMENT_SPLIT
-  if (tr && tile && im->adjq_ok && getenv("TRK_ADJQ_SPLIT")) nsplit = 1;      // (timing experiment: the quad kernel splits by itself)
-#endif
-  const bool adjq = tr && tile && im->adjq_ok && tile_T == 32 && nsplit == 1 && !adjq_riders && getenv("TRK_RADON_NO_ADJQ") == nullptr;
-  const int adjq_th = N / 64;
-  const int64_t adjq_blocks = (int64_t)adjq_th * adjq_th;
   if (epi.on && (batch != 1 || (tr && !tile))) return fail(TRK_EUNSUPPORTED, "radon: fused epilogue needs batch 1 and the tiled adjoint");
   // the forward's band reduction carries the epilogue / the fused norm / the adjoint's records
   const bool post = epi.on || im->n_bands > 1 || ext_part;
   if (ext_part) sumsq = ext_part;          // where a finished value goes when the partials do not fit / no kernel makes any
   const bool fuse_ssq = sumsq && batch == 1 && (tr ? tile : post);
   const int64_t post_blocks = ceil_div((int64_t)nt * na * ndp, 256);
-  const int64_t n_part = tr ? (adjq ? adjq_blocks : adj_blocks) * nt : post_blocks;
+  const int64_t n_part = tr ? ap.blocks * nt : post_blocks;
   epi.pq = PostReq{};
   if (tr && tile && batch == 1 && epi.on && op->post.on) {
     epi.pq = op->post;                         // trk_gk_step_post: the mailbox post on the adjoint kernel's first workgroup
@@ -2704,10 +2638,18 @@ int radon_run(trk_op* op, int tr, const float* x, int64_t ldx, float* y, int64_t
     return finalize_sums(ssq_part, (int)n_part, 1, 1, sumsq, s);
   };
   if (!tr) {
+    // a hinted forward leaves the records for the adjoint that follows where that adjoint reads k_radon_adj_prep's records (the
+    // mirrored-pair adjoint reads records of its own kind, made by its own pre-pass: nothing to leave behind for it).  The plan is
+    // asked without riders: an adjoint that carries them takes a tile route all the same and then makes its records itself.
+    bool want_rec = false;
+    if ((hints & HINT_OUT_FEEDS_OPPOSITE) && batch == 1) {
+      const AdjPath next = adj_path(im, 1, /*riders=*/false);
+      want_rec = next.prep && next.kind != AdjKind::quad && next.kind != AdjKind::simple;
+    }
     for (int b = 0; b < batch; ++b) {  // the transposed copy is per vector
       const float* xb = x + (int64_t)b * ldx;
       const FwdPath fp = fwd_path(im, xb);
-      const bool lds = fp.lds, dma = fp.dma;
+      const bool lds = fp.lds;
       // the adjoint that produced xb may have left its transpose in xT already (hinted chain): then the copy costs nothing and the
       // kernel without the transposing staging is the faster one (512^2 x 180 inside Golub-Kahan: 24.5 vs 27.6 us)
       const bool have_xT = im->n_mode1 > 0 && (hints & HINT_INPUT_FROM_OPPOSITE) && im->xT_src == xb;
@@ -2725,53 +2667,34 @@ int radon_run(trk_op* op, int tr, const float* x, int64_t ldx, float* y, int64_t
       const int64_t bs = (int64_t)nt * na * nd;
       dim3 grid(ndblk * ngrp * nt, nb, 1);
       float* yb = y + (int64_t)b * ldy;
-      static const bool no_rec_out = getenv("TRK_RADON_NO_REC_OUT") != nullptr;     // tuning knobs: the producer side of the hints off
-      // (the mirrored-pair adjoint reads records of its own kind, made by its own pre-pass: nothing to leave behind for it)
-      const bool want_rec = (hints & HINT_OUT_FEEDS_OPPOSITE) && tile && adj_prep && batch == 1 && !no_rec_out &&
-                            !(im->adjq_ok && tiles32 >= 1024 && getenv("TRK_RADON_NO_ADJQ") == nullptr);
-      // measured: 512^2 35 us (shared) vs 32 us (per-wave windows); 2048^2 0.256 vs 0.277 ms; 4096^2 0.96 vs 1.11 ms
       if (band_res) {
         const int rows = im->band, nbr = N / rows;
-        static const int slice_env = getenv("TRK_RADON_BANDRES_SLICES") ? atoi(getenv("TRK_RADON_BANDRES_SLICES")) : 0;
         // one workgroup of 16 waves per CU whatever the width (measured at 32 frames of 256^2: two workgroups of 8 waves per CU, which the
         // narrower band's LDS would allow, 18.4 us against 16.5)
         const size_t lds_bytes = sizeof(float) * (size_t)rows * (N + 2 * BR_PAD) + 16;
-        static const int per_cu_env = getenv("TRK_RADON_BANDRES_PER_CU") ? atoi(getenv("TRK_RADON_BANDRES_PER_CU")) : 1;
-        const int per_cu = (per_cu_env >= 2 && 2 * (lds_bytes + 512) <= 160 * 1024) ? 2 : 1;
-        int nslice = slice_env > 0 ? slice_env : (cu_count() * per_cu + nt * 2 * nbr / 2) / (nt * 2 * nbr);
+        int nslice = (cu_count() + nt * 2 * nbr / 2) / (nt * 2 * nbr);
         if (nslice < 1) nslice = 1;
         static bool attr_set = false;
         if (!attr_set) {
           TRK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_radon_fwd_band), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
           attr_set = true;
         }
-        hipLaunchKernelGGL(k_radon_fwd_band, dim3((unsigned)(nt * 2 * nbr * nslice)), dim3(per_cu >= 2 ? BR_NT / 2 : BR_NT), lds_bytes, s, xb, im->xT, im->part, N, nd, im->ang_dev,
-                           na, im->adj_ang, im->adj_n0, nslice, bs, im->A32, im->B32, im->npad,
-#ifdef TRK_RADON_BAND_EXPERIMENT
-                           (have_xT ? 1 : 0) | (getenv("TRK_RADON_BAND_X") ? atoi(getenv("TRK_RADON_BAND_X")) & 6 : 0), rows);
-#else
-                           have_xT ? 1 : 0, rows);
-#endif
+        hipLaunchKernelGGL(k_radon_fwd_band, dim3((unsigned)(nt * 2 * nbr * nslice)), dim3(BR_NT), lds_bytes, s, xb, im->xT, im->part, N, nd, im->ang_dev,
+                           na, im->adj_ang, im->adj_n0, nslice, bs, im->A32, im->B32, im->npad, have_xT ? 1 : 0, rows);
       } else if (fp.win) {
         // window-sharing kernel: band partials of rays no window owns must read as zero
         if (hipMemsetAsync(im->part, 0, sizeof(float) * (size_t)nb * bs, s) != hipSuccess) return fail(TRK_EHIP, "radon: hipMemsetAsync failed");
         if (fp.quad) {
           const int nwq = ceil_div(N + im->band + 4, QD_WO), ngq = ceil_div(im->nq, 4);
           dim3 gq(8 * ceil_div(nwq, 8) * ngq * nt, nb, 1);           // windows dealt to the XCDs in contiguous eighths (see the kernel)
-          // tiles in flight per workgroup: 2 where the chip is full of workgroups anyway (four per CU hide each other's staging round
-          // trips), 4 where it is not (the chain of a workgroup's chunks is then bound by ONE round trip per chunk: see the kernel)
-          static const int qbuf_env = getenv("TRK_RADON_QBUF") ? atoi(getenv("TRK_RADON_QBUF")) : 0;
-          const int64_t wgs = (int64_t)nwq * ngq * nt * nb;
-          // (measured: deeper staging does not pay at any size — the extra LDS costs resident workgroups, 512^2: 40 -> 60 us with four
-          //  tiles in flight, 4096^2: 0.76 -> 1.34 ms; the knob stays for experiments)
-          (void)wgs;
-          const int qbuf = qbuf_env ? qbuf_env : 2;
+          // two tiles in flight per workgroup (measured: deeper staging does not pay at any size — the extra LDS costs resident
+          // workgroups, 512^2: 40 -> 60 us with four tiles in flight, 4096^2: 0.76 -> 1.34 ms)
           // round 6: the lean kernel for the workgroups its plan allows, k_radon_fwd_quad for the listed rest (TRK_RADON_NO_QUADF=1: all
           // of them, as rounds 4-5).  The plan depends on the geometry and the grid only: made at the first apply, kept with the handle
           const bool no_quadf = getenv("TRK_RADON_NO_QUADF") != nullptr;      // read per call: the tests switch it
           dim3 gslow = gq;
           const int* wg_list = nullptr;
-          if (!no_quadf && qbuf == 2) {
+          if (!no_quadf) {
             if (!im->qplan || im->qplan_gx != (int)gq.x || im->qplan_nb != nb) {
               if (im->qplan) (void)hipFree(im->qplan);
               if (im->qslow) (void)hipFree(im->qslow);
@@ -2793,24 +2716,19 @@ int radon_run(trk_op* op, int tr, const float* x, int64_t ldx, float* y, int64_t
             gslow = dim3((unsigned)im->qslow_n, 1, 1);
             wg_list = im->qslow;
           }
-#define QUAD(NB) hipLaunchKernelGGL(k_radon_fwd_quad<NB>, gslow, dim3(256), 0, s, xb, im->xT, im->part, N, nd, im->quad_dev, im->nq, ngq, na, nwq, bs, im->band, \
-                                    im->fidx, im->A32q, im->B32q, im->npad, im->ang_dev, im->A32, im->B32, wg_list, (int)gq.x)
-          if (gslow.x > 0) {
-            if (qbuf >= 4) QUAD(4); else if (qbuf == 3) QUAD(3); else QUAD(2);
-          }
-#undef QUAD
+          if (gslow.x > 0)
+            hipLaunchKernelGGL(k_radon_fwd_quad<2>, gslow, dim3(256), 0, s, xb, im->xT, im->part, N, nd, im->quad_dev, im->nq, ngq, na, nwq, bs,
+                               im->band, im->fidx, im->A32q, im->B32q, im->npad, im->ang_dev, im->A32, im->B32, wg_list, (int)gq.x);
         } else {
           const int nwin = ceil_div(N + 2 * im->band + 16, 61);
           dim3 gw(nwin * ngrp * nt, nb, 1);
           hipLaunchKernelGGL(k_radon_fwd_win<0>, gw, dim3(256), 0, s, xb, im->xT, im->part, N, nd, im->ang_dev, na, ngrp, nwin, bs, im->band, im->fidx, im->A32, im->B32, im->npad);
         }
       } else if (!post) {
-        if (lds && dma) hipLaunchKernelGGL((k_radon_fwd_lds<true, true>), grid, dim3(256), 0, s, xb, im->xT, yb, N, nd, im->ang_dev, na, ngrp, ndblk, bs, im->band, im->A32, im->B32, im->npad, direct1);
-        else if (lds) hipLaunchKernelGGL(k_radon_fwd_lds<true>, grid, dim3(256), 0, s, xb, im->xT, yb, N, nd, im->ang_dev, na, ngrp, ndblk, bs, im->band, im->A32, im->B32, im->npad, direct1);
+        if (lds) hipLaunchKernelGGL((k_radon_fwd_lds<true, true>), grid, dim3(256), 0, s, xb, im->xT, yb, N, nd, im->ang_dev, na, ngrp, ndblk, bs, im->band, im->A32, im->B32, im->npad, direct1);
         else hipLaunchKernelGGL(k_radon_fwd<true>, grid, dim3(256), 0, s, xb, im->xT, yb, N, nd, im->ang_dev, na, ngrp, ndblk, bs, im->band, im->A32, im->B32, im->npad);
       } else {
-        if (lds && dma) hipLaunchKernelGGL((k_radon_fwd_lds<false, true>), grid, dim3(256), 0, s, xb, im->xT, im->part, N, nd, im->ang_dev, na, ngrp, ndblk, bs, im->band, im->A32, im->B32, im->npad, direct1);
-        else if (lds) hipLaunchKernelGGL(k_radon_fwd_lds<false>, grid, dim3(256), 0, s, xb, im->xT, im->part, N, nd, im->ang_dev, na, ngrp, ndblk, bs, im->band, im->A32, im->B32, im->npad, direct1);
+        if (lds) hipLaunchKernelGGL((k_radon_fwd_lds<false, true>), grid, dim3(256), 0, s, xb, im->xT, im->part, N, nd, im->ang_dev, na, ngrp, ndblk, bs, im->band, im->A32, im->B32, im->npad, direct1);
         else hipLaunchKernelGGL(k_radon_fwd<false>, grid, dim3(256), 0, s, xb, im->xT, im->part, N, nd, im->ang_dev, na, ngrp, ndblk, bs, im->band, im->A32, im->B32, im->npad);
       }
       if (post) {
@@ -2831,38 +2749,20 @@ int radon_run(trk_op* op, int tr, const float* x, int64_t ldx, float* y, int64_t
   } else {
     for (int b = 0; b < batch; ++b) {            // the record array is per vector
       const float* xb = x + (int64_t)b * ldx;
-      if (adjq) {
-        static const bool no_xt_out_q = getenv("TRK_RADON_NO_XT_OUT") != nullptr;
-        float* xT_out = ((hints & HINT_OUT_FEEDS_OPPOSITE) && im->n_mode1 > 0 && batch == 1 && !no_xt_out_q) ? im->xT : nullptr;
+      float* yb = y + (int64_t)b * ldy;
+      float* xT_out = ((hints & HINT_OUT_FEEDS_OPPOSITE) && tile && im->n_mode1 > 0 && batch == 1) ? im->xT : nullptr;
+      if (ap.kind == AdjKind::quad) {
         hipLaunchKernelGGL(k_radon_adj_prepq, dim3(ceil_div((int64_t)im->nq * 4 * ndp, 256), nt), dim3(256), 0, s, xb, im->recq, nd, na, im->nq,
                            im->quad_dev, im->wq, im->A32q);
         im->rec_src = nullptr;
-        static const int qb_env = getenv("TRK_RADON_ADJQ_QB") ? atoi(getenv("TRK_RADON_ADJQ_QB")) : 0;
-        if (qb_env == 2)
-          hipLaunchKernelGGL(k_radon_adj_quad<2>, dim3((unsigned)adjq_blocks, nt), dim3(256), 0, s, im->recq, y + (int64_t)b * ldy, N, nd, im->nq,
-                             im->adjq, im->CBq, im->npad, adjq_th, ssq_part, epi, xT_out);
-        else
-#ifdef TRK_ADJQ_EXPERIMENT_SPLIT
-          hipLaunchKernelGGL(k_radon_adj_quad<4>, dim3((unsigned)adjq_blocks, nt, getenv("TRK_ADJQ_SPLIT") ? atoi(getenv("TRK_ADJQ_SPLIT")) : 1), dim3(256), 0, s, im->recq, y + (int64_t)b * ldy, N, nd, im->nq,
-                             im->adjq, im->CBq, im->npad, adjq_th, ssq_part, epi, xT_out);
-#else
-          hipLaunchKernelGGL(k_radon_adj_quad<4>, dim3((unsigned)adjq_blocks, nt), dim3(256), 0, s, im->recq, y + (int64_t)b * ldy, N, nd, im->nq,
-                             im->adjq, im->CBq, im->npad, adjq_th, ssq_part, epi, xT_out);
-#endif
-        if (xT_out) im->xT_src = y + (int64_t)b * ldy;
-        TRK_LAUNCH_CHECK();
-        continue;
-      }
-      if (adj_prep) {
+      } else if (ap.prep) {
         if (!((hints & HINT_INPUT_FROM_OPPOSITE) && im->rec_src == xb))   // else: the forward that produced xb left its records
           hipLaunchKernelGGL(k_radon_adj_prep, dim3(ceil_div((int64_t)na * ndp, 256), nt), dim3(256), 0, s, xb, im->rec, nd, na,
                              im->adj_ang, im->adj_wgt, im->A32);
         im->rec_src = nullptr;
       }
-      static const bool no_xt_out = getenv("TRK_RADON_NO_XT_OUT") != nullptr;
-      float* xT_out = ((hints & HINT_OUT_FEEDS_OPPOSITE) && tile && im->n_mode1 > 0 && batch == 1 && !no_xt_out) ? im->xT : nullptr;
-      if (nsplit > 1) {
-        const int64_t need = (int64_t)nsplit * nt * adj_blocks * 1024, need_c = (int64_t)nt * adj_blocks;
+      if (ap.nsplit > 1) {
+        const int64_t need = (int64_t)ap.nsplit * nt * ap.blocks * 1024, need_c = (int64_t)nt * ap.blocks;
         if (im->adj_part_cap < need) {
           if (im->adj_part) hipFree(im->adj_part);
           im->adj_part = nullptr;
@@ -2879,38 +2779,35 @@ int radon_run(trk_op* op, int tr, const float* x, int64_t ldx, float* y, int64_t
           im->adj_cnt_cap = need_c;
         }
       }
-#define ADJ_TILE(TT, PP, BB, PR)                                                                                              \
-  hipLaunchKernelGGL((k_radon_adj_tile<TT, PP, BB, PR>), dim3((unsigned)(adj_blocks * nsplit), nt), dim3(256), 0, s, xb, im->rec, \
-                     y + (int64_t)b * ldy, N, nd, na, im->adj_ang, im->adj_wgt, im->A32, im->adj_n0, im->CB, im->npad, tiles_x, \
-                     ssq_part, epi, xT_out, nsplit, im->adj_part, im->adj_cnt)
-      // the parts of a tile as groups of ONE workgroup where that gives about one workgroup per CU (512^2: 256 tiles)
-      static const int grp_env = getenv("TRK_RADON_ADJ_GROUPS") ? atoi(getenv("TRK_RADON_ADJ_GROUPS")) : 1;
-      const bool groups = grp_env != 0 && tile && tile_T == 32 && nsplit == 4 && adj_blocks * nt <= cu_count() && adj_blocks * nt * 4 >= 3 * cu_count();
-      if (groups) {
-        if (adj_prep) hipLaunchKernelGGL((k_radon_adj_tile<32, 4, 8, true, 4>), dim3((unsigned)adj_blocks, nt), dim3(1024), 0, s, xb, im->rec,
-                                         y + (int64_t)b * ldy, N, nd, na, im->adj_ang, im->adj_wgt, im->A32, im->adj_n0, im->CB, im->npad, tiles_x,
-                                         ssq_part, epi, xT_out, 1, im->adj_part, im->adj_cnt);
-        else hipLaunchKernelGGL((k_radon_adj_tile<32, 4, 8, false, 4>), dim3((unsigned)adj_blocks, nt), dim3(1024), 0, s, xb, im->rec,
-                                y + (int64_t)b * ldy, N, nd, na, im->adj_ang, im->adj_wgt, im->A32, im->adj_n0, im->CB, im->npad, tiles_x,
-                                ssq_part, epi, xT_out, 1, im->adj_part, im->adj_cnt);
-      } else if (tile && tile_T == 32) {
-        // (16 angles per batch — half the barriers, twice the rings — measured at 512^2 x 180: 34.7 us against 29.9; not instantiated)
-        // (TRK_RADON_ADJ_AB=16 — one batch for a 15-angle frame, half the barriers at 180 angles — measured again in round 6 on C5's
-        //  shape, 32 frames of 256^2 x 15 angles: see profiles/r06/adj_ab16.txt)
-        if (ab_env == 16) { if (adj_prep) ADJ_TILE(32, 4, 16, true); else ADJ_TILE(32, 4, 16, false); }
-        else if (adj_prep) ADJ_TILE(32, 4, 8, true); else ADJ_TILE(32, 4, 8, false);
-      } else if (tile && (ab_env ? ab_env == 16 : (na > 32 || adj_blocks * nt <= 4 * (int64_t)cu_count()))) {
-        // (16 angles per batch also for the few frames of a dynamic problem one rank of eight holds — 4 frames of 256^2 x 15 angles, 1 024
-        //  workgroups: 10.2 -> 9.1 us per apply, profiles/r06/adj_ab16.txt; with more workgroups than that the shorter batches win)
-        if (adj_prep) ADJ_TILE(16, 1, 16, true); else ADJ_TILE(16, 1, 16, false);
-      } else if (tile) {   // few angles per frame (dynamic problems: 15): short batches, so that staging and gathering still overlap
-        if (adj_prep) ADJ_TILE(16, 1, 4, true); else ADJ_TILE(16, 1, 4, false);
+      // groups: the four parts of a tile in one workgroup of 1024 threads (nsplit = 1 to the kernel); else nsplit workgroups per tile
+#define ADJ_TILE(TT, PP, BB, PR, G, NSPLIT)                                                                                          \
+  hipLaunchKernelGGL((k_radon_adj_tile<TT, PP, BB, PR, G>), dim3((unsigned)(ap.blocks * NSPLIT), nt), dim3(256 * G), 0, s, xb, im->rec, \
+                     yb, N, nd, na, im->adj_ang, im->adj_wgt, im->A32, im->adj_n0, im->CB, im->npad, ap.tiles_x, ssq_part, epi, xT_out,  \
+                     NSPLIT, im->adj_part, im->adj_cnt)
+      switch (ap.kind) {
+        case AdjKind::quad:
+          hipLaunchKernelGGL(k_radon_adj_quad<4>, dim3((unsigned)ap.blocks, nt), dim3(256), 0, s, im->recq, yb, N, nd, im->nq, im->adjq,
+                             im->CBq, im->npad, N / 64, ssq_part, epi, xT_out);
+          break;
+        case AdjKind::groups:
+          if (ap.prep) ADJ_TILE(32, 4, 8, true, 4, 1); else ADJ_TILE(32, 4, 8, false, 4, 1);
+          break;
+        case AdjKind::tile32_b8:
+          if (ap.prep) ADJ_TILE(32, 4, 8, true, 1, ap.nsplit); else ADJ_TILE(32, 4, 8, false, 1, ap.nsplit);
+          break;
+        case AdjKind::tile16_b16:
+          if (ap.prep) ADJ_TILE(16, 1, 16, true, 1, 1); else ADJ_TILE(16, 1, 16, false, 1, 1);
+          break;
+        case AdjKind::tile16_b4:
+          if (ap.prep) ADJ_TILE(16, 1, 4, true, 1, 1); else ADJ_TILE(16, 1, 4, false, 1, 1);
+          break;
+        case AdjKind::simple:
+          hipLaunchKernelGGL(k_radon_adj_simple, dim3((unsigned)ap.blocks, nt), dim3(256), 0, s, im->rec, yb, N, nd, na, im->adj_ang,
+                             im->adj_n0, im->CB, im->npad, (double*)nullptr);
+          break;
       }
 #undef ADJ_TILE
-      else
-        hipLaunchKernelGGL(k_radon_adj_simple, dim3((unsigned)adj_blocks, nt), dim3(256), 0, s, im->rec, y + (int64_t)b * ldy, N, nd, na,
-                           im->adj_ang, im->adj_n0, im->CB, im->npad, (double*)nullptr);
-      if (xT_out) im->xT_src = y + (int64_t)b * ldy;
+      if (xT_out) im->xT_src = yb;
       TRK_LAUNCH_CHECK();
     }
     if (ssq_part) {
@@ -2988,8 +2885,7 @@ int radon_apply_axpby(trk_op* op, int tr, const float* x, Coef a, Coef b, const 
     if (int rc = radon_apply_refmode(op, tr, x, tr ? op->rows : op->cols, im->ref_tmp, nout, 1, nullptr, s)) return rc;
     return ref_axpby_f32(nout, a, im->ref_tmp, b, z, out, sumsq, s);
   }
-  const bool tile = getenv("TRK_RADON_ADJ_SIMPLE") == nullptr && im->N >= 16;
-  if (tr && !tile) {
+  if (tr && adj_path(im, 1, op->post.on || op->lsqr.on).kind == AdjKind::simple) {
     if (int rc = radon_run(op, tr, x, op->rows, out, op->cols, 1, nullptr, Epi{}, 0, s)) return rc;
     return trk_axpby(op->cols, a.c, a.num, a.den, a.flags, out, b.c, b.num, b.den, b.flags, z, out, sumsq, (trk_stream)s);
   }
@@ -3198,14 +3094,10 @@ static int radon_create_impl(int N, int n_det, const double* angles, int nt, int
   // small images: a 64-row band of the image fits the LDS of a CU (k_radon_fwd_band).  TRK_RADON_NO_BANDRES=1: the per-wave windows
   const bool band_res = N % BR_ROWS == 0 && N >= 2 * BR_ROWS && N <= BR_NMAX && getenv("TRK_RADON_NO_BANDRES") == nullptr;
   if (band_res) band = br_rows(N);
-  if (const char* e = getenv("TRK_RADON_BAND")) {               // tuning knob; kept a positive multiple of RADON_CHUNK
-    band = atoi(e);
-    band = band < RADON_CHUNK ? RADON_CHUNK : (band / RADON_CHUNK) * RADON_CHUNK;
-  }
   const int nb = (N + band - 1) / band;
   auto* im = new RadonImpl{};
   im->N = N; im->nd = n_det; im->na = na; im->nt = nt; im->n_mode1 = n1; im->npad = npad; im->n_bands = nb; im->band = band;
-  im->band_res = (band_res && band == br_rows(N)) ? 1 : 0;
+  im->band_res = band_res ? 1 : 0;
   hipError_t e = hipSuccess;
   auto up = [&](void** dst, const void* src, size_t bytes) {
     if (e == hipSuccess) e = hipMalloc(dst, bytes);
@@ -3230,7 +3122,8 @@ static int radon_create_impl(int N, int n_det, const double* angles, int nt, int
   // the mirrored-pair adjoint: images of whole 64 x 64 super-tiles, mostly complete quads (single angles would pay for four), from
   // 2048^2 on (measured per apply, 180 angles, k_radon_adj_tile -> k_radon_adj_quad: 4096^2 1.009 -> 0.794 ms, 2048^2 0.263 -> 0.222,
   // 1024^2 0.084 -> 0.101: 256 workgroups of four sub-phases leave the chip half empty there).  TRK_RADON_ADJQ_MIN: the tests' knob
-  const int adjq_min = getenv("TRK_RADON_ADJQ_MIN") ? atoi(getenv("TRK_RADON_ADJQ_MIN")) : 2048;
+  const char* adjq_min_env = getenv("TRK_RADON_ADJQ_MIN");
+  const int adjq_min = adjq_min_env ? atoi(adjq_min_env) : 2048;
   im->adjq_ok = (nq > 0 && N % 64 == 0 && N >= adjq_min && adjq_mostly_full && (int64_t)nq * 4 * ndp * 16 < ((int64_t)1 << 31)) ? 1 : 0;
   if (im->adjq_ok) {
     up((void**)&im->adjq, adjq_h.data(), sizeof(AdjQuad) * adjq_h.size());

@@ -53,11 +53,8 @@ template <bool NTL> __device__ __forceinline__ i4u ldm4(const int* p) {
 // for the 2-lane rows (first differences, framelets: at most two products per chain) as "almost free" — measured in round 6
 // (profiles/r06/spmv_ab.txt): first differences 2048^2 forward 48 -> 57 us, transpose 36 -> 45, space-time differences 20 -> 24, framelets
 // 129 -> 138, and the one deviation it was meant for (MMGKS with the framelet regulariser, `Residual` against the reference) 3.2e-4 -> 2.2e-4:
-// the deviation is not the SpMV's.  Not adopted; -DTRK_CSR_EXPERIMENT_F64_CHAINS builds it.
+// the deviation is not the SpMV's.  Not adopted.
 template <int G> struct ChainT { typedef float type; };
-#ifdef TRK_CSR_EXPERIMENT_F64_CHAINS                // (A/B build switch; see the note above: measured, not adopted)
-template <> struct ChainT<2> { typedef double type; };
-#endif
 __device__ __forceinline__ float chain_fma(float v, float x, float a) { return fmaf(v, x, a); }
 __device__ __forceinline__ double chain_fma(float v, float x, double a) { return fma((double)v, (double)x, a); }
 

@@ -1830,13 +1830,6 @@ __global__ __launch_bounds__(NT, MINB) void k_wgram_tv(const float* __restrict__
   constexpr int NP = T * (T + 1) / 2;
   const int lockstep = lockstep_in & 1;
   const bool no_xcd_map = (lockstep_in & 2) != 0;                // TRK_WGRAM_TV_NO_XCD=1: the round-robin unit order (A/B)
-#ifdef TRK_WGRAM_TV_EXPERIMENT
-  // timing experiments only (tools/r05_wgram_exp.sh builds a separate library with this macro; the product never defines it and
-  // the results are WRONG with either bit): 4 = no wave fetches the column right of its strips, 8 = the loads alone, no arithmetic
-  const bool x_nohalo = (lockstep_in & 4) != 0, x_loadonly = (lockstep_in & 8) != 0;
-#else
-  constexpr bool x_nohalo = false, x_loadonly = false;
-#endif
   __shared__ double red[3][4][64];
   __shared__ __attribute__((aligned(16))) float wl[NT / 64][Z ? 96 : 64];
   // lockstep (the launcher's choice when the workgroup's four waves always own four neighbouring strips of one band): the pixel
@@ -1902,7 +1895,7 @@ __global__ __launch_bounds__(NT, MINB) void k_wgram_tv(const float* __restrict__
     const int c0 = cs + 8 * sl;
     const bool last_strip = cs + 32 >= N;                        // (uniform) no pixel right of this strip
     const int nxo = last_strip ? 31 : 32;                        // clamped: a valid address, met by a zero weight
-    const bool need_nx = (!lockstep || wave == NT / 64 - 1) && !x_nohalo;   // (uniform per wave)
+    const bool need_nx = !lockstep || wave == NT / 64 - 1;      // (uniform per wave)
 
     // every load is unconditional (clamped addresses, zeroed weights instead of branches): all loads of a row are in flight together
     auto load = [&](TvRow<T>& P, int i) {
@@ -1925,11 +1918,6 @@ __global__ __launch_bounds__(NT, MINB) void k_wgram_tv(const float* __restrict__
       }
     };
     auto step = [&](const TvRow<T>& P, const TvRow<T>& Q, int i) {   // P: image row i, Q: the one below
-      if (x_loadonly) {
-#pragma unroll
-        for (int t = 0; t < T; ++t) accz[t] += (double)(P.x[t][0].x + P.x[t][1].w + P.nx[t] + P.w + (Z ? P.z : 0.f));
-        return;
-      }
       float nbr[T];
 #pragma unroll
       for (int t = 0; t < T; ++t) nbr[t] = P.nx[t];
@@ -2048,7 +2036,7 @@ __global__ __launch_bounds__(NT, MINB) void k_wgram_tv(const float* __restrict__
 
 // ------------------------------------------------------------------ the same pass, the rows of V through LDS in FULL lines (round 5)
 // k_wgram_tv's loads are fragment-shaped: one wave-instruction touches 16 basis vectors x 64 bytes, a workgroup 512 contiguous bytes
-// per (vector, image row) — the loads ALONE take the kernel's whole time (tools/r05_wgram_exp.sh: k = 32 at 4096^2 576 us with the
+// per (vector, image row) — the loads ALONE take the kernel's whole time (a timing build, round 5: k = 32 at 4096^2 576 us with the
 // arithmetic removed, 545 with it; 3.9 TB/s where the plain streams of k_gemv_n run at 5.9).  Here a workgroup of 8 waves owns 256
 // image columns: every (vector, image row) of its tile is ONE 1 KiB global_load_lds_dwordx4 (a whole wave reading 1 KiB of one
 // row of one basis vector) straight into an LDS stage, four stages deep — two image rows in flight per CU without a register held
@@ -3150,11 +3138,7 @@ static int wgram_tv_run(const float* V, int64_t ld, int k, int N, const float* w
   if (int rc = scratch_doubles(s, (size_t)bx * nv + ((size_t)PROBE_ROWS + 1) * 2 * 2 * PROBE_P, &part)) return rc;
   double* probe_part = part + (size_t)bx * nv;
   double* probe_sums = probe_part + (size_t)PROBE_ROWS * 2 * 2 * PROBE_P;
-#ifdef TRK_WGRAM_TV_EXPERIMENT
-  static const int no_xcd = (env_int("TRK_WGRAM_TV_NO_XCD", 0) ? 2 : 0) | (env_int("TRK_WGRAM_TV_X", 0) & 12);
-#else
   static const int no_xcd = env_int("TRK_WGRAM_TV_NO_XCD", 0) ? 2 : 0;
-#endif
   // Which arithmetic forms the tile products (trk_wgram_tv_precision; environment TRK_WGRAM_TV_F32=1 / TRK_WGRAM_TV_PIECES=2|3 set the
   // process default): 1 auto (default: two bf16 pieces unless the probe finds the data's roundings correlated, then the fp32 pipe),
   // 0 fp32 matrix pipe, 2 two bf16 pieces, 3 three bf16 pieces
