@@ -794,6 +794,27 @@ int trk_cgls_iterate_sharded(trk_op* A, trk_comm* comm, int k_first, int n_iters
                              double* S, double* G4, double* NP, int np_capacity_blocks, int* n_np_inout, double* PG, int pcap,
                              int* n_g_inout, trk_stream stream);
 
+/* ---------------------------------------------------------------------------------------------- dense float64 SVD (dense_svd.hip)
+ * One-sided (Hestenes) block Jacobi for the direct solvers (tSVD, tGSVD, Tikhonov; docs/kernels/dense_svd.md).
+ * trk_dense_svd_f64_dims: for an m x n problem (m >= n, n <= TRK_DENSE_SVD_MAX_COLS) the padded column count *npad (a multiple of
+ *   32) and the workspace the call needs, in doubles.
+ * trk_dense_svd_f64: A (device, column-major, lda >= m) is left untouched.  G (ldg >= m, npad columns) receives A V, whose columns
+ *   are mutually orthogonal to the relative tolerance `tol` (of order m * eps; for two columns of very different size, to tol
+ *   times the square of the larger norm); V (ldv >= npad, npad columns) the accumulated
+ *   orthogonal rotation (its leading n x n block is the right factor; the rest is the identity); S[0..n) = ||G_j||.  Columns are NOT
+ *   sorted or normalised: U_j = G_j / S_j (0 where S_j = 0) in descending order of S is the caller's step.  *sweeps = sweeps run
+ *   (at most max_sweeps; the last one is the sweep that found every pair orthogonal), *converged = 1 when that sweep happened.
+ *   Bitwise reproducible (fixed summation orders, no atomics).  Two host synchronisations per sweep (the column order by norm, the
+ *   sweep's verdict).
+ * trk_dense_gemv_f64: y = beta y + alpha op(A) (d .* x), op(A) = A^T (trans = 1: y has n entries, x and d m) or A (trans = 0: y has
+ *   m entries, x and d n); d may be NULL (all ones); beta = 0 does not read y.  Fixed summation order. */
+#define TRK_DENSE_SVD_MAX_COLS 8192
+int trk_dense_svd_f64_dims(int64_t m, int64_t n, int64_t* npad, int64_t* work_doubles);
+int trk_dense_svd_f64(const double* A, int64_t m, int64_t n, int64_t lda, double* G, int64_t ldg, double* V, int64_t ldv, double* S,
+                      double* work, int64_t work_doubles, double tol, int max_sweeps, int* sweeps, int* converged, trk_stream stream);
+int trk_dense_gemv_f64(int trans, int64_t m, int64_t n, const double* A, int64_t lda, const double* x, const double* d, double alpha,
+                       double beta, double* y, trk_stream stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB_PATH = os.path.join(CSRC, "libtrk.so")
-SOURCES = ["core.hip", "vecops.hip", "blur2d.hip", "tvops.hip", "radon2d.hip", "spmv.hip", "fanbeam2d.hip", "projected.hip", "cgls_loop.hip", "comm.hip", "cgls_tiled.hip", "cgls_sharded.hip", "ref64.hip"]
+SOURCES = ["core.hip", "vecops.hip", "blur2d.hip", "tvops.hip", "radon2d.hip", "spmv.hip", "fanbeam2d.hip", "projected.hip", "cgls_loop.hip", "comm.hip", "cgls_tiled.hip", "cgls_sharded.hip", "ref64.hip", "dense_svd.hip"]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-I" + INCLUDE, "-I" + CSRC]
 
 
@@ -308,6 +308,10 @@ SIGNATURES = {
     "trk_wgram_tv_z": (c_int, [c_f32p, c_i64, c_int, c_int, c_f32p, c_f64p, c_f32p, c_f64p, c_stream]),
     "trk_wgram_tv": (c_int, [c_f32p, c_i64, c_int, c_int, c_f32p, c_f64p, c_stream]),
     "trk_wgram": (c_int, [c_f32p, c_i64, c_int, c_i64, c_f32p, c_f32p, c_f64p, c_f64p, c_f64p, c_stream]),
+    "trk_dense_svd_f64_dims": (c_int, [c_i64, c_i64, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
+    "trk_dense_svd_f64": (c_int, [c_f64p, c_i64, c_i64, c_i64, c_f64p, c_i64, c_f64p, c_i64, c_f64p, c_f64p, c_i64, c_dbl, c_int,
+                                  ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_stream]),
+    "trk_dense_gemv_f64": (c_int, [c_int, c_i64, c_i64, c_f64p, c_i64, c_f64p, c_f64p, c_dbl, c_dbl, c_f64p, c_stream]),
 }
 
 _lib = None

@@ -6,6 +6,11 @@ computed by the engine (trips_py_amd/krylov.py).
     golub_kahan_update(A, U, S, V)   -> one more GK step                                                    (:230-255)
     arnoldi_update(A, V, H)          -> one more Arnoldi step                                               (:207-228)
 
+and the dense SVD of the direct solvers (tSVD, Tikhonov): the float64 one-sided Jacobi SVD of csrc/dense_svd.hip
+(docs/kernels/dense_svd.md):
+
+    svd(A)                           -> (U m x k, S k, Vh k x n), k = min(m, n), S descending (np.linalg.svd(full_matrices=False))
+
 The `*_update` functions accept either the reference's arrays (NumPy, n x k) — then the bases are uploaded, one step is
 taken and NumPy arrays come back, O(k n) traffic like the reference's own hstack — or the handles they returned the
 previous time (`KrylovArrays`), in which case the bases stay on the GPU and the step costs two operator applies.
@@ -178,3 +183,15 @@ def arnoldi_update(A, V, H):
         st.gram, st.capacity, st.by_gram = None, None, False   # a cold start from host arrays: sweep by sweep (the basis may grow)
     st.step()
     return KrylovArrays(st.V.numpy(), st), st.H()
+
+
+def svd(A, max_sweeps=None):
+    """Thin float64 SVD on the device: A = U diag(S) Vh with U m x k, Vh k x n, k = min(m, n), S descending.
+
+    A: NumPy array, np.matrix, scipy.sparse matrix, an engine operator (densified through todense()) or a torch tensor.  NumPy
+    arrays come back for host inputs, float64 device tensors for torch inputs.  At most 8192 columns (of A or of A^T)."""
+    from . import _dense
+    Ut, S, Vt, _ = _dense.svd_device(A, **({} if max_sweeps is None else {"max_sweeps": max_sweeps}))
+    if isinstance(A, torch.Tensor):
+        return Ut.T, S, Vt
+    return Ut.T.cpu().numpy(), S.cpu().numpy(), Vt.cpu().numpy()

@@ -96,9 +96,55 @@ def _diagonalise(R_A, R_L, rhs):
     return sig, U.T @ rhs
 
 
-def generalized_crossvalidation(R_A, R_L, rhs, variant="standard", fullsize=None, **_ignored):
+def truncation_gcv(bproj, n, gcvtype, resid2=0.0, rows=None, p=None):
+    """The direct solvers' GCV truncation index (gcv.py:96-123), from bhat = Q^T b.
+
+    'tsvd':  G(k) = (sum_{j >= k} bhat_j^2) / (rows - k)^2 for k = n-1, ..., 0, where the sum runs over every entry of bhat
+             (those past n included) and `resid2` adds the squared norm of the part of b outside the columns of a thin Q; rows =
+             len(bhat) unless given.  Returns the k of the smallest G (k = n is never a candidate); of equal values the larger k.
+    'tgsvd': G(i) = (sum_{j < n-1-i} bhat_j^2 + sum_{j >= n} bhat_j^2 + resid2) / (p - 1 - i)^2 for i = 0, ..., n-1 (p defaults
+             to n).  Returns i itself, not the number of kept columns.  The denominator is zero at i = p - 1: for p = n (what a
+             tGSVD with a square X passes) that is the last candidate; for p < n it lies inside the range, and for p > n there is
+             none.  A zero denominator gives inf, or nan for a zero numerator, which like the reference's min() never wins
+             unless it comes first.
+    The numerators are running sums over bhat (O(n)) where the reference sums each candidate afresh: on a tie to the last
+    bits the two may pick different indices."""
+    b2 = np.square(np.asarray(bproj, dtype=np.float64).reshape(-1))
+    n = int(n)
+    if n < 1 or b2.size < n:
+        raise ValueError(f"truncation_gcv: need n >= 1 and at least n entries of bhat (n = {n}, {b2.size} entries)")
+    beyond = float(np.sum(b2[n:])) + float(resid2)
+    i = np.arange(n)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        if gcvtype == "tsvd":
+            rows = b2.size if rows is None else int(rows)
+            dropped = np.cumsum(b2[:n][::-1])                      # dropped[i] = sum_{j >= n-1-i} bhat_j^2
+            vals = (dropped + beyond) / np.square(float(rows) - (n - 1 - i).astype(np.float64))
+        elif gcvtype == "tgsvd":
+            p = n if p is None else int(p)
+            kept = np.concatenate(([0.0], np.cumsum(b2[:n])))[n - 1 - i]   # sum_{j < n-1-i} bhat_j^2
+            vals = (kept + beyond) / np.square((p - 1 - i).astype(np.float64))
+        else:
+            raise ValueError(f"gcvtype={gcvtype!r}: 'tikhonov', 'tsvd' or 'tgsvd'")
+    if np.isnan(vals[0]):
+        best = 0
+    else:
+        best = int(np.argmin(np.where(np.isnan(vals), np.inf, vals)))
+    return n - 1 - best if gcvtype == "tsvd" else best
+
+
+def generalized_crossvalidation(R_A, R_L, rhs, variant="standard", fullsize=None, gcvtype="tikhonov", resid2=0.0, **_ignored):
     """lambda = argmin G over [1e-9, 1e2] by bounded Brent search, same settings as gcv.py:94-95.  The pair is first
-    brought to (diag(s), I) — it already is in the hybrid solvers — so that every one of the ~60 evaluations is O(k)."""
+    brought to (diag(s), I) — it already is in the hybrid solvers — so that every one of the ~60 evaluations is O(k).
+
+    gcvtype = 'tsvd' / 'tgsvd': the direct solvers' truncation index instead (truncation_gcv): `rhs` is then bhat = Q^T b, R_L gives
+    the column count n (and, for 'tgsvd', p = its row count), R_A is not looked at; with a thin Q, `resid2` = ||b - Q Q^T b||^2 and
+    `fullsize` = the row count of the full problem."""
+    if gcvtype in ("tsvd", "tgsvd"):
+        shp = np.shape(R_L)
+        return truncation_gcv(rhs, shp[1], gcvtype, resid2=resid2, rows=fullsize, p=shp[0] if gcvtype == "tgsvd" else None)
+    if gcvtype != "tikhonov":
+        raise ValueError(f"generalized_crossvalidation: gcvtype={gcvtype!r}; 'tikhonov', 'tsvd' or 'tgsvd'")
     rhs = np.asarray(rhs, dtype=np.float64).reshape(-1)
     R_A, R_L = np.asarray(R_A, dtype=np.float64), np.asarray(R_L, dtype=np.float64)
     k = R_A.shape[0]
