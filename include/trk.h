@@ -274,7 +274,7 @@ int trk_gk_step(trk_op* op, int k, const float* u_k, const float* v_prev, float*
  * result.  V: rows of ld floats (row k is written), w: n floats of scratch, G: the basis' Gram matrix so far (ldg x ldg doubles, rows
  * 0..k-2 installed; row k-1 is installed here), W: 2k doubles of scratch, S: S[0] = h_{k+1,k}^2, S[1..1+k) = column k of H above it.
  * Optional: the same five calls in one — same results bit for bit, in five kernels where the five calls launch seven (the two
- * finalize launches are folded into their consumers; TRK_ARNOLDI_7=1 in the environment keeps the seven). */
+ * finalize launches are folded into their consumers). */
 int trk_arnoldi_step(trk_op* op, float* V, int64_t ld, int k, float* w, double* G, int ldg, double* W, double* S, trk_stream stream);
 /* The same step whose last kernel also posts S[offset .. offset + count) to host[offset ..] of `mb` (trk_mailbox_post's contract:
  * trk_mailbox_wait(mb, slot) returns once they have arrived) — no launch for the post. */
@@ -463,7 +463,7 @@ int trk_host_worker_collect(trk_host_worker* w, double* lam_out, int* have_out);
  * and a bidiagonal SVD that rotates the one vector, no singular vectors formed — y = (G_A + lam G_L)^-1 c by a Cholesky factorisation of
  * the sum (the normal equations of the stacked problem [R_A; sqrt(lam) R_L] y = [Q_A^T b; 0] the reference hands to lstsq; R_A, R_L being
  * Cholesky factors of the Gram matrices, both see the same conditioning; the stacked problem by pivoted QR where the sum does not
- * factor, or with TRK_GRAM_GCV_LSTSQ set).  c_select / c_solve: the right-hand side the selector sees and the one the solve uses (MMGKS
+ * factor).  c_select / c_solve: the right-hand side the selector sees and the one the solve uses (MMGKS
  * hands the weighted and the unweighted one, MMGKS.py:97-106; GKS the same array twice).  lapack: {dpotrf, dtrtrs, dgebrd, dormbr,
  * dbdsqr, dgelsy}, the caller's LAPACK as plain C pointers (Fortran calling convention).  *ok_out = 0: a factorisation failed
  * (semi-definite Gram matrix, singular R_L, no convergence) and nothing was written: the caller's own branches take over. */
@@ -648,8 +648,7 @@ int trk_wgram_tv(const float* V, int64_t ld, int k, int N, const float* w, doubl
  *                two-piece split would lose — max |S' - S| / sqrt(S_aa S_bb) of the sampled Gram with
  *                and without the split, in float64 — and the verdict stays on the DEVICE: ONE Gram launch holds both arithmetic forms, every
  *                workgroup works the verdict out from the probe's sums in its prologue and takes the sweep of the form it names — two pieces
- *                below 3e-7, the fp32 pipe above (nothing visits the host; the probe reads ~24 MB whatever the image size).  TRK_WGRAM_TV_AUTO_PAIR=1
- *                selects the older A/B arrangement instead (a gated PAIR of launches, one of which returns at once).
+ *                below 3e-7, the fp32 pipe above (nothing visits the host; the probe reads ~24 MB whatever the image size).
  *                <= 1e-6 per entry relative to sqrt(G_aa G_bb) on data the sample represents; the piecewise-
  *                constant / repeated-value images of tests/test_gpu_kernels.py trip it, noisy images and Krylov vectors do not.
  *   2            each weighted difference split into TWO bf16 pieces, all four partial products: what is lost is each operand's third
@@ -660,8 +659,7 @@ int trk_wgram_tv(const float* V, int64_t ld, int k, int N, const float* w, doubl
  *   0            the fp32 matrix pipe (v_mfma_f32_16x16x4_f32): fp32 products, <= 1e-6 likewise, 0.51-0.57 ms at 4096^2 whatever k.
  * Returns the mode in force before the call; mode -1 only queries.  PROCESS-WIDE and NOT THREAD-SAFE: one plain global read by every
  * trk_wgram_tv* call on any stream — a caller that switches it around a solve (MMGKS(gram_precision=)) must not run another solve on
- * another thread meanwhile (the engine's model is one process per GPU, one solve at a time).  Environment TRK_WGRAM_TV_F32=1 /
- * TRK_WGRAM_TV_PIECES=2|3 set the default. */
+ * another thread meanwhile (the engine's model is one process per GPU, one solve at a time). */
 int trk_wgram_tv_precision(int mode);
 /* Diagnostics: {verdict (0 two pieces ran, 1 the fp32 pipe ran), the sampled deviation} of the LAST call in mode 1, copied to two host
  * doubles after a device synchronisation; {-1, -1} before the first such call.  (The record is written by workgroup 0 of the Gram launch

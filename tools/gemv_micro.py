@@ -1,8 +1,6 @@
 """The basis kernels of the projection solvers alone, at the C4 shape (n = 4096^2 fp32 rows): out = base - V c (trk_gemv_n, + sum of
 squares), x = V y (trk_gemv_n), V^T [r, r2] (trk_gemv_t2), V^T [4 right-hand sides] (trk_gemv_tn), V^T r (trk_gemv_t) — time per
-launch and bytes of basis streamed per second, over basis sizes k.  Knobs (environment, read by the library):
-TRK_GEMVN_UNROLL = 4 / 8 / 16 (basis rows requested together), TRK_GEMVN_GRID (blocks per CU), TRK_GEMVT_PER_CU (blocks per CU of the
-transposed family), TRK_NT (cache hints).   usage: [GEMV_MICRO_K=4,8,...] python3 tools/gemv_micro.py [N]"""
+launch and bytes of basis streamed per second, over basis sizes k.   usage: [GEMV_MICRO_K=4,8,...] python3 tools/gemv_micro.py [N]"""
 import os
 import sys
 
@@ -38,7 +36,6 @@ def timeit(fn, reps=10):
     return e0.elapsed_time(e1) / reps * 1e3          # us
 
 
-print("knobs:", {k: v for k, v in os.environ.items() if k.startswith("TRK_")})
 print(f"{'k':>3} | {'gemv_n base+ss':>16} | {'gemv_n plain':>16} | {'gemv_t2':>16} | {'gemv_tn(4)':>16} | {'gemv_t':>16}   (us, TB/s of 4 k n + vectors)")
 for k in KS:
     cells = []

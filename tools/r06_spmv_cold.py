@@ -1,5 +1,5 @@
 """CSR SpMV on the 16-frame Joseph block-diagonal matrix (bench.py's next_sparse_dynamic), COLD: three handles holding copies of the matrix
-take turns, so every apply streams its 170 MB from HBM.  TRK_CSR_GROUP=<lanes per row> forces the group size (read when the handle is made)."""
+take turns, so every apply streams its 170 MB from HBM."""
 import importlib.util
 import os
 import sys
@@ -23,7 +23,7 @@ xs = [torch.rand(n, device=dev) for _ in range(3)]
 ys = [torch.empty(m, device=dev) for _ in range(3)]
 zs = [torch.empty(n, device=dev) for _ in range(3)]
 alg = 8.0 * nnz + 4.0 * (m + n)
-row = [f"TRK_CSR_GROUP={os.environ.get('TRK_CSR_GROUP', 'rule')}"]
+row = []
 for name in ("fwd", "adj"):
     for mode, nh in (("cold", 3), ("warm", 1)):
         def fn(i):

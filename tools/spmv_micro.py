@@ -1,5 +1,5 @@
 """CSR SpMV (csrc/spmv.hip) alone: the block-diagonal Joseph matrix of bench.py's next_sparse_dynamic leg and the regulariser matrices
-(first differences, framelets) — time per apply, GB/s of 8 nnz + 4 (m + n).  TRK_CSR_GROUP=<2..64> forces the lanes per row."""
+(first differences, framelets) — time per apply, GB/s of 8 nnz + 4 (m + n)."""
 import importlib.util
 import os
 import sys

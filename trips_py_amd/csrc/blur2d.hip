@@ -687,8 +687,6 @@ inline void slide_grid(int nx, int ny, int batch, int kh, int U, int* spans_x, i
     }
     if (last) break;
   }
-  static const int rpb_env = getenv("TRK_BLUR_RPB") ? atoi(getenv("TRK_BLUR_RPB")) : 0;   // tuning knob (rows per band)
-  if (rpb_env > 0) rpb = rpb_env;
   *spans_x = sx;
   *nbands = ceil_div(nx, rpb);
   *rows_per_band = rpb;

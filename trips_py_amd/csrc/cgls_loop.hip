@@ -18,10 +18,8 @@ extern "C" {
 // Measured (iterations/s, 0 vs 1): 512^2 39.1 k vs 38.3 k, 1536^2 23.7 k vs 23.4 k | 3072^2 10.6 k vs 11.1 k, 3584^2 8.30 k vs
 // 8.72 k, 4096^2 6.85 k vs 7.26 k, 4608^2 5.48 k vs 5.70 k, 5120^2 4.45 k vs 4.36 k, 6144^2 2.82 k vs 2.74 k, 8192^2 1.53 k vs
 // 1.64 k: the saved pass pays from ~8 M unknowns on (small images are launch-bound and the five-stream kernel is the
-// slower one per byte).  TRK_CGLS_XP=0/1 overrides (tuning).
+// slower one per byte).
 int trk_cgls_update_grouping(int64_t n) {
-  static const int env = getenv("TRK_CGLS_XP") ? atoi(getenv("TRK_CGLS_XP")) : -1;
-  if (env >= 0) return env != 0;
   return n >= ((int64_t)8 << 20) ? 1 : 0;
 }
 

@@ -513,32 +513,13 @@ int trk_gk_step(trk_op* op, int k, const float* u_k, const float* v_prev, float*
 // The five library calls the Python step made, enqueued by one: on the 512^2 blur the host was the bound (65 % device-busy).
 // Five kernels (round 6; seven before): the finalize launches of the two reductions are gone — the 2k sums of the sweep are added up
 // by the workgroups of the launch whose last arriver runs the k x k recurrence (k_finalize_cgs), the norm by every workgroup of the
-// normalising pass (k_scale_fin); both in k_finalize's own association: the bits of the seven-kernel form (TRK_ARNOLDI_7=1 keeps it).
+// normalising pass (k_scale_fin); both in k_finalize's own association: the bits of the seven-kernel form.
 static int arnoldi_step_impl(trk_op* op, float* V, int64_t ld, int k, float* w, double* G, int ldg, double* W, double* S,
                              const PostReq& post, hipStream_t s, const float* dotv = nullptr, double* dot_out = nullptr) {
   const int64_t n = op->rows;
   const float* vk1 = V + (int64_t)(k - 1) * ld;
   float* vk = V + (int64_t)k * ld;
-  static const bool seven = getenv("TRK_ARNOLDI_7") && atoi(getenv("TRK_ARNOLDI_7"));
   if (int rc = trk_op_apply(op, 0, vk1, n, w, n, 1, nullptr, s)) return rc;
-  if (seven) {
-    if (int rc = trk_gemv_t2(V, ld, k, n, w, vk1, W, s)) return rc;                   // h = V^T w | Gram row of V[k-1]
-    if (int rc = trk_cgs_coeffs(G, ldg, W, W + k, k, 2, S + 1, s)) return rc;         // column k of H (without its last entry) at S[1..1+k)
-    if (int rc = trk_gemv_n(V, ld, k, n, S + 1, 1.0, w, -1.0, vk, S, s)) return rc;   // V[k] = w - V c, S[0] = ||.||^2
-    if (int rc = trk_axpby(n, 1.0, nullptr, S, TRK_SQRT_DEN, vk, 0.0, nullptr, nullptr, 0, nullptr, vk, nullptr, s)) return rc;
-    if (dotv) {
-      if (int rc = trk_dot(vk, dotv, n, dot_out, s)) return rc;
-      if (post.on && post.sum_host) {                    // (the seven-kernel form posts the dot by a launch of its own, ahead of the step's)
-        hipLaunchKernelGGL(k_mailbox_post, dim3(1), dim3(64), 0, s, (const double*)dot_out, post.sum_host, 1, post.seq, post.value - 1);
-        TRK_LAUNCH_CHECK();
-      }
-    }
-    if (post.on) {
-      hipLaunchKernelGGL(k_mailbox_post, dim3(1), dim3(64), 0, s, post.src, post.dst, post.count, post.seq, post.value);
-      TRK_LAUNCH_CHECK();
-    }
-    return TRK_OK;
-  }
   double* part = nullptr;
   int nblk = 0;
   if (int rc = gemv_t2_partials(V, ld, k, n, w, vk1, &part, &nblk, s)) return rc;

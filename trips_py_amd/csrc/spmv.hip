@@ -4,7 +4,7 @@
 // into per-frame blocks (trips/utilities/io.py:132-135,197-229; demos/2_demo_dynamic_CrossPhantom.ipynb).  y = A x uses the CSR
 // of A; y = A^T x uses the CSR of A^T (built once by the host) — both directions are gathers (no atomics).
 //
-// One kernel, k_csr_group<G>: a GROUP of G = 2 .. 64 neighbouring lanes owns a row (G = the largest power of two not above a quarter of the
+// One kernel, k_csr_group<G>: a GROUP of G = 2 .. 16 neighbouring lanes owns a row (G = the largest power of two not above a quarter of the
 // mean row length, 2 .. 16: 2 for first-difference and framelet rows, 16 for tomography rays), the wave's 64 / G groups own neighbouring
 // rows — so the wave's loads of `vals` and `indices` are contiguous runs whatever the row length (round 4's one-thread-per-row
 // kernel read rows of 2 .. 9 non-zeros with a stride of the row length across lanes) — every lane keeps four fp32 FMA chains,
@@ -35,19 +35,15 @@ struct SpImpl {
   Csr a, at;
 };
 
-// (non-temporal loads of the matrix streams — nothing of them is re-read within an apply — LOSE: 38 -> 59 us on the Joseph matrix;
-//  TRK_CSR_NT=1 keeps the variant for measurements)
-template <bool NTL> __device__ __forceinline__ float ldm(const float* p) { return NTL ? __builtin_nontemporal_load(p) : *p; }
-template <bool NTL> __device__ __forceinline__ int ldm(const int* p) { return NTL ? __builtin_nontemporal_load(p) : *p; }
+// Loads of the matrix streams.  Plain loads: non-temporal ones — nothing of them is re-read within an apply — LOST, 38 -> 59 us on the
+// Joseph matrix.  (Through these helpers, not indexed off the kernel's __restrict__ arguments: that schedules the kernel differently.)
 // four consecutive entries of a stream in one 16-byte load at 4-byte alignment (a row starts wherever indptr says)
 typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
 typedef int i4u __attribute__((ext_vector_type(4), aligned(4)));
-template <bool NTL> __device__ __forceinline__ f4u ldm4(const float* p) {
-  return NTL ? __builtin_nontemporal_load(reinterpret_cast<const f4u*>(p)) : *reinterpret_cast<const f4u*>(p);
-}
-template <bool NTL> __device__ __forceinline__ i4u ldm4(const int* p) {
-  return NTL ? __builtin_nontemporal_load(reinterpret_cast<const i4u*>(p)) : *reinterpret_cast<const i4u*>(p);
-}
+__device__ __forceinline__ float ldm(const float* p) { return *p; }
+__device__ __forceinline__ int ldm(const int* p) { return *p; }
+__device__ __forceinline__ f4u ldm4(const float* p) { return *reinterpret_cast<const f4u*>(p); }
+__device__ __forceinline__ i4u ldm4(const int* p) { return *reinterpret_cast<const i4u*>(p); }
 
 // Accumulator type of the per-lane chains: fp32 (four chains per lane, float64 only across the group).  ADVICE r05 suggested float64 chains
 // for the 2-lane rows (first differences, framelets: at most two products per chain) as "almost free" — measured in round 6
@@ -69,12 +65,13 @@ __device__ __forceinline__ double chain_fma(float v, float x, double a) { return
 // is left is the gathers of x, 17.7 M of them fetching a 64-byte sector each.  A lane's four chains take the four entries of its quads;
 // what is left of a row after its last whole quad (<= 3 entries) goes to lanes 0 .. 2 on their first chain.  Every column of a batch keeps
 // this order: bit-identical to its single apply, as before.
-template <int G, int KB, bool SUMSQ, bool NTL, bool V4>
+template <int G, int KB, bool SUMSQ>
 __global__ __launch_bounds__(NT) void k_csr_group(int64_t nrows, const unsigned* __restrict__ indptr,
                                                   const int* __restrict__ indices, const float* __restrict__ vals,
                                                   const float* __restrict__ x, int64_t ldx, float* __restrict__ y, int64_t ldy,
                                                   double* __restrict__ partials, int pstride) {
   typedef typename ChainT<G>::type acc_t;
+  constexpr bool V4 = G >= 8;
   __shared__ double red[NT / 64];
   const int g = threadIdx.x & (G - 1);
   // Rows in CONTIGUOUS spans per workgroup, the spans dealt to the XCDs in contiguous eighths (round 6; workgroups b and b + 8 share an
@@ -106,8 +103,8 @@ __global__ __launch_bounds__(NT) void k_csr_group(int64_t nrows, const unsigned*
       unsigned q = g;
       for (; q + G < nq; q += 2 * G) {                                 // two quads of each stream in flight per lane
         const unsigned ba = p0 + 4 * q, bb = p0 + 4 * (q + G);
-        const f4u va = ldm4<NTL>(vals + ba), vb = ldm4<NTL>(vals + bb);
-        const i4u ca = ldm4<NTL>(indices + ba), cb = ldm4<NTL>(indices + bb);
+        const f4u va = ldm4(vals + ba), vb = ldm4(vals + bb);
+        const i4u ca = ldm4(indices + ba), cb = ldm4(indices + bb);
 #pragma unroll
         for (int b = 0; b < KB; ++b) {
           const float* __restrict__ xb = x + (int64_t)b * ldx;
@@ -125,8 +122,8 @@ __global__ __launch_bounds__(NT) void k_csr_group(int64_t nrows, const unsigned*
       }
       if (q < nq) {
         const unsigned ba = p0 + 4 * q;
-        const f4u va = ldm4<NTL>(vals + ba);
-        const i4u ca = ldm4<NTL>(indices + ba);
+        const f4u va = ldm4(vals + ba);
+        const i4u ca = ldm4(indices + ba);
 #pragma unroll
         for (int b = 0; b < KB; ++b) {
           const float* __restrict__ xb = x + (int64_t)b * ldx;
@@ -139,8 +136,8 @@ __global__ __launch_bounds__(NT) void k_csr_group(int64_t nrows, const unsigned*
       {                                                                 // the row's last <= 3 entries: lanes 0 .. 2, first chain
         const unsigned pt = p0 + 4 * nq + g;
         const bool ht = g < 3 && pt < p1;
-        const float vt = ht ? ldm<NTL>(vals + pt) : 0.f;
-        const int ct = ht ? ldm<NTL>(indices + pt) : 0;
+        const float vt = ht ? ldm(vals + pt) : 0.f;
+        const int ct = ht ? ldm(indices + pt) : 0;
 #pragma unroll
         for (int b = 0; b < KB; ++b) {
           const float* __restrict__ xb = x + (int64_t)b * ldx;
@@ -160,9 +157,9 @@ __global__ __launch_bounds__(NT) void k_csr_group(int64_t nrows, const unsigned*
         float v[8];
         int c[8];
 #pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = ldm<NTL>(vals + p + u * G);
+        for (int u = 0; u < 8; ++u) v[u] = ldm(vals + p + u * G);
 #pragma unroll
-        for (int u = 0; u < 8; ++u) c[u] = ldm<NTL>(indices + p + u * G);
+        for (int u = 0; u < 8; ++u) c[u] = ldm(indices + p + u * G);
         for (;;) {
           float xv[8];
 #pragma unroll
@@ -172,9 +169,9 @@ __global__ __launch_bounds__(NT) void k_csr_group(int64_t nrows, const unsigned*
           float vn[8];
           int cn[8];
 #pragma unroll
-          for (int u = 0; u < 8; ++u) vn[u] = more ? ldm<NTL>(vals + pn + u * G) : 0.f;
+          for (int u = 0; u < 8; ++u) vn[u] = more ? ldm(vals + pn + u * G) : 0.f;
 #pragma unroll
-          for (int u = 0; u < 8; ++u) cn[u] = more ? ldm<NTL>(indices + pn + u * G) : 0;
+          for (int u = 0; u < 8; ++u) cn[u] = more ? ldm(indices + pn + u * G) : 0;
           a0[0] = chain_fma(v[0], xv[0], a0[0]);
           a1[0] = chain_fma(v[1], xv[1], a1[0]);
           a2[0] = chain_fma(v[2], xv[2], a2[0]);
@@ -195,8 +192,8 @@ __global__ __launch_bounds__(NT) void k_csr_group(int64_t nrows, const unsigned*
     }
     // four loads of each stream in flight per lane, four independent chains per column (long rows: a wave streams 2 KB per trip)
     for (; p + 3 * G < p1; p += 4 * G) {
-      const float v0 = ldm<NTL>(vals + p), v1 = ldm<NTL>(vals + p + G), v2 = ldm<NTL>(vals + p + 2 * G), v3 = ldm<NTL>(vals + p + 3 * G);
-      const int c0 = ldm<NTL>(indices + p), c1 = ldm<NTL>(indices + p + G), c2 = ldm<NTL>(indices + p + 2 * G), c3 = ldm<NTL>(indices + p + 3 * G);
+      const float v0 = ldm(vals + p), v1 = ldm(vals + p + G), v2 = ldm(vals + p + 2 * G), v3 = ldm(vals + p + 3 * G);
+      const int c0 = ldm(indices + p), c1 = ldm(indices + p + G), c2 = ldm(indices + p + 2 * G), c3 = ldm(indices + p + 3 * G);
 #pragma unroll
       for (int b = 0; b < KB; ++b) {
         const float* __restrict__ xb = x + (int64_t)b * ldx;
@@ -209,8 +206,8 @@ __global__ __launch_bounds__(NT) void k_csr_group(int64_t nrows, const unsigned*
     // up to three more, issued together (predicated: a row's tail, or the whole of a short row)
     if (!V4) {
       const bool h0 = p < p1, h1 = p + G < p1, h2 = p + 2 * G < p1;
-      const float v0 = h0 ? ldm<NTL>(vals + p) : 0.f, v1 = h1 ? ldm<NTL>(vals + p + G) : 0.f, v2 = h2 ? ldm<NTL>(vals + p + 2 * G) : 0.f;
-      const int c0 = h0 ? ldm<NTL>(indices + p) : 0, c1 = h1 ? ldm<NTL>(indices + p + G) : 0, c2 = h2 ? ldm<NTL>(indices + p + 2 * G) : 0;
+      const float v0 = h0 ? ldm(vals + p) : 0.f, v1 = h1 ? ldm(vals + p + G) : 0.f, v2 = h2 ? ldm(vals + p + 2 * G) : 0.f;
+      const int c0 = h0 ? ldm(indices + p) : 0, c1 = h1 ? ldm(indices + p + G) : 0, c2 = h2 ? ldm(indices + p + 2 * G) : 0;
 #pragma unroll
       for (int b = 0; b < KB; ++b) {
         const float* __restrict__ xb = x + (int64_t)b * ldx;
@@ -243,17 +240,9 @@ __global__ __launch_bounds__(NT) void k_csr_group(int64_t nrows, const unsigned*
 
 template <int G, int KB>
 void launch_group(const Csr& M, int grid, const float* xb, int64_t ldx, float* yb, int64_t ldy, double* pb, hipStream_t s) {
-  static const bool ntl = getenv("TRK_CSR_NT") && atoi(getenv("TRK_CSR_NT")) != 0;
-  static const bool no_v4 = getenv("TRK_CSR_NO_VEC4") && atoi(getenv("TRK_CSR_NO_VEC4")) != 0;     // (the entry-per-lane form everywhere)
-  constexpr bool V = G >= 8;
-#define CG(SS, NN, VV) hipLaunchKernelGGL((k_csr_group<G, KB, SS, NN, VV>), dim3(grid), dim3(NT), 0, s, M.nrows, M.indptr, M.indices, M.vals, xb, ldx, yb, ldy, pb, grid)
-  if (V && !no_v4) {
-    if (pb) { if (ntl) CG(true, true, V); else CG(true, false, V); }
-    else    { if (ntl) CG(false, true, V); else CG(false, false, V); }
-  } else {
-    if (pb) { if (ntl) CG(true, true, false); else CG(true, false, false); }
-    else    { if (ntl) CG(false, true, false); else CG(false, false, false); }
-  }
+#define CG(SS) hipLaunchKernelGGL((k_csr_group<G, KB, SS>), dim3(grid), dim3(NT), 0, s, M.nrows, M.indptr, M.indices, M.vals, xb, ldx, yb, ldy, pb, grid)
+  if (pb) CG(true);
+  else CG(false);
 #undef CG
 }
 
@@ -263,9 +252,7 @@ void launch_cols(const Csr& M, int grid, const float* xb, int64_t ldx, float* yb
     case 2: launch_group<2, KB>(M, grid, xb, ldx, yb, ldy, pb, s); break;
     case 4: launch_group<4, KB>(M, grid, xb, ldx, yb, ldy, pb, s); break;
     case 8: launch_group<8, KB>(M, grid, xb, ldx, yb, ldy, pb, s); break;
-    case 16: launch_group<16, KB>(M, grid, xb, ldx, yb, ldy, pb, s); break;
-    case 32: launch_group<32, KB>(M, grid, xb, ldx, yb, ldy, pb, s); break;
-    default: launch_group<64, KB>(M, grid, xb, ldx, yb, ldy, pb, s); break;
+    default: launch_group<16, KB>(M, grid, xb, ldx, yb, ldy, pb, s); break;
   }
 }
 
@@ -276,8 +263,7 @@ int sp_apply(trk_op* op, int tr, const float* x, int64_t ldx, float* y, int64_t 
   // groups cover the rows once up to 16 workgroups per CU, grid-stride beyond (first differences of a 2048^2 image, 8.4 M rows of 2:
   // 55 us with one group per row, 46 with the cap; longer rows: no difference); a reduction leaves <= kMaxPartialBlocks partials
   int64_t want = (M.nrows * M.group + NT - 1) / NT;
-  static const int64_t cap_env = getenv("TRK_CSR_GRID_PER_CU") ? atoll(getenv("TRK_CSR_GRID_PER_CU")) * cu_count() : 0;
-  int64_t cap = cap_env > 0 ? cap_env : (int64_t)cu_count() * 16;
+  int64_t cap = (int64_t)cu_count() * 16;
   if (sumsq && cap > kMaxPartialBlocks) cap = kMaxPartialBlocks;
   if (want > cap) want = cap;
   const int grid = (int)(want < 1 ? 1 : want);
@@ -285,17 +271,16 @@ int sp_apply(trk_op* op, int tr, const float* x, int64_t ldx, float* y, int64_t 
   if (sumsq)
     if (int rc = scratch_doubles(s, (size_t)grid * batch, &part)) return rc;
   // columns per pass (round 6): a batch — `A @ V`, GKS.py:37 / MMGKS.py:44 — goes through in passes of 8 / 4 / 2 columns, each pass
-  // reading the matrix once; TRK_CSR_COLS=1 restores one launch per column (A/B runs)
-  static const int max_cols = getenv("TRK_CSR_COLS") ? atoi(getenv("TRK_CSR_COLS")) : 8;
+  // reading the matrix once
   TimerScope tm(op->timer, op->timer_which, tr, s);
   for (int b = 0; b < batch;) {
     const float* xb = x + (int64_t)b * ldx;
     float* yb = y + (int64_t)b * ldy;
     double* pb = part ? part + (size_t)b * grid : nullptr;
     const int left = batch - b;
-    if (left >= 8 && max_cols >= 8) { launch_cols<8>(M, grid, xb, ldx, yb, ldy, pb, s); b += 8; }
-    else if (left >= 4 && max_cols >= 4) { launch_cols<4>(M, grid, xb, ldx, yb, ldy, pb, s); b += 4; }
-    else if (left >= 2 && max_cols >= 2) { launch_cols<2>(M, grid, xb, ldx, yb, ldy, pb, s); b += 2; }
+    if (left >= 8) { launch_cols<8>(M, grid, xb, ldx, yb, ldy, pb, s); b += 8; }
+    else if (left >= 4) { launch_cols<4>(M, grid, xb, ldx, yb, ldy, pb, s); b += 4; }
+    else if (left >= 2) { launch_cols<2>(M, grid, xb, ldx, yb, ldy, pb, s); b += 2; }
     else { launch_cols<1>(M, grid, xb, ldx, yb, ldy, pb, s); b += 1; }
   }
   tm.stop();
@@ -323,14 +308,8 @@ int csr_upload(Csr& c, int64_t nrows, int64_t ncols, int64_t nnz, const int64_t*
   // us per apply): rows of 17 (Joseph transpose, 17.7 M non-zeros) 16 / 8 / 4 lanes -> 68.8 / 42.8 / 30.6; rows of 431 (Joseph)
   // 64 / 32 / 16 -> 38.4 / 36.7 / 36.2; rows of 169 (framelet transpose) 64 / 32 / 16 -> 162 / 134 / 112; rows of 7 (framelets)
   // 4 / 2 -> 139 / 108: many short chains per wave keep more loads in flight than one long coalesced one.
-  // TRK_CSR_GROUP=<2..64> forces it, -1 / -2 halve / quarter the rule's choice (tuning).
   int group = 2;
   while (group < 16 && (int64_t)8 * group * nrows <= nnz) group *= 2;
-  if (const char* e = getenv("TRK_CSR_GROUP")) {
-    const int v = atoi(e);
-    if (v == 2 || v == 4 || v == 8 || v == 16 || v == 32 || v == 64) group = v;
-    if (v < 0 && group > 2 && -v <= 3) group = group >> (-v) < 2 ? 2 : group >> (-v);
-  }
   c = Csr{nrows, ncols, nnz, nullptr, nullptr, nullptr, group};
   std::vector<unsigned> ip32((size_t)nrows + 1);
   for (int64_t r = 0; r <= nrows; ++r) {

@@ -299,7 +299,7 @@ __device__ __forceinline__ double scalar_from_wave(const ScalarSrc s, int lane) 
 inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
 // Cache hints for the streamed vectors of the large-image CGLS loop, as a mask: stores — bit 0 the blur kernel's output,
-// bit 1 the new iterate x' (bits 2, 3: the residual and the direction: measured, no gain); loads in the [x, p] update —
+// bit 1 the new iterate x' (the residual and the direction were measured too: no gain); loads in the [x, p] update —
 // bit 4 the old iterate x, bit 5 t = A^T r (both read exactly once).  What a kernel finds in the 256 MB memory-side
 // cache decides its speed, and everything that is not re-read soon only evicts what is:
 //   below ~11.5 M floats the next kernel finds plain-stored data cached and hints lose (2048^2: 18.7 k vs 16.6 k
@@ -309,16 +309,9 @@ inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 //   loop 51 -> 36 us; 6144^2: 2.78 k -> 3.01 k (79 -> 50 us); 8192^2: 1.59 k -> 1.70 k; 4608^2: 5.60 k -> 5.71 k.
 // Bits 6, 7: the basis rows read by k_gemv_t / k_gemv_n (k x 4n bytes streamed once per kernel; hinted, they stop evicting
 // the vector every row tile re-reads): 4096^2 GKS 343 -> 372, Hybrid-GMRES 907 -> 1001, MMGKS 331 -> 342 iterations/s.
-// TRK_NT=<mask> overrides (tuning).
-// Bit 8 (TRK_REV=1, an experiment — DESIGN.md 4.1b): the two CGLS update kernels sweep their vectors from the END: each then meets
-// the rows its producer (a blur launch, sweeping forward) wrote last first, while they can still be in the 256 MB memory-side cache,
-// and leaves its own output so that the next blur launch meets ITS first rows last-written.
 inline int stream_nontemporal(int64_t n) {
-  static const int env = getenv("TRK_NT") ? atoi(getenv("TRK_NT")) : -1;
-  static const int rev = (getenv("TRK_REV") && atoi(getenv("TRK_REV"))) ? 256 : 0;
-  if (env >= 0) return env | rev;
-  if (n >= kNontemporalLoadsMinFloats) return 51 | 192 | rev;
-  return (n >= kNontemporalMinFloats ? (3 | 192) : 0) | rev;
+  if (n >= kNontemporalLoadsMinFloats) return 51 | 192;
+  return n >= kNontemporalMinFloats ? (3 | 192) : 0;
 }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }

@@ -15,11 +15,6 @@ constexpr int NT = 256;
 // grid for a streaming kernel over n floats: one float4 per thread until the chip is covered 4x (<= kMaxPartialBlocks
 // blocks so a reduction leaves at most that many partials), then grid-stride
 
-inline int env_int(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v ? atoi(v) : dflt;
-}
-
 // Workgroups of `kernel` (NT threads, no dynamic LDS) that one CU holds at a time.
 template <class K>
 inline int resident_blocks_per_cu(K kernel) {
@@ -33,13 +28,11 @@ inline int resident_blocks_per_cu(K kernel) {
 // Measured (4096^2, k = 18, three tiles): 683 x 3 = 2049 workgroups, one more than the chip holds, ran 290 us; 1024 x 3 (two
 // rounds) 222 us; a single full round is what every basis size gets now (tools/gemv_micro.py, profiles/r03/gemv_micro.txt).
 inline int tiled_dot_grid_x(int64_t n, int ntile, int blocks_per_cu) {
-  static const int env = env_int("TRK_GEMVT_PER_CU", 0);
-  const int64_t total = (int64_t)cu_count() * (env > 0 ? env : blocks_per_cu);
+  const int64_t total = (int64_t)cu_count() * blocks_per_cu;
   int64_t bx = total / ntile;
   // float4s of a row per thread at least: two on short vectors (512^2: one float4 per thread and row left a workgroup little but its
-  // reduction to do; Hybrid-GMRES 17.0 -> 17.4 k iterations/s, four: 17.0), TRK_GEMVT_F4 overrides
-  static const int env_f4 = env_int("TRK_GEMVT_F4", 0);
-  const int per_thread = env_f4 > 0 ? env_f4 : (n <= ((int64_t)1 << 20) ? 2 : 1);
+  // reduction to do; Hybrid-GMRES 17.0 -> 17.4 k iterations/s, four: 17.0)
+  const int per_thread = n <= ((int64_t)1 << 20) ? 2 : 1;
   const int64_t chunk = (int64_t)NT * 4 * per_thread;
   const int64_t want = (n + chunk - 1) / chunk;
   if (bx > want) bx = want;
@@ -339,15 +332,14 @@ __global__ __launch_bounds__(NT) void k_cgls_update(int64_t n, int64_t m, Scalar
         s2 += e0 * e0 + e1 * e1 + e2 * e2 + e3 * e3;
       }
     }
-    for (int64_t i0 = tid; i0 < m4; i0 += nth) {
-      const int64_t i = (nt & 256) ? m4 - 1 - i0 : i0;      // TRK_REV: last-written rows of the producer first (Infinity-Cache experiment)
+    for (int64_t i = tid; i < m4; i += nth) {
       float4 rv = ld4(r, i);
       const float4 wv = ld4(w, i);
       rv.x = fmaf(-step, wv.x, rv.x);
       rv.y = fmaf(-step, wv.y, rv.y);
       rv.z = fmaf(-step, wv.z, rv.z);
       rv.w = fmaf(-step, wv.w, rv.w);
-      if (nt & 4) st4_nt(r, i, rv); else st4(r, i, rv);
+      st4(r, i, rv);
     }
   }
   for (int64_t i = ntail + tid; i < n; i += nth) {
@@ -377,7 +369,7 @@ __global__ __launch_bounds__(NT) void k_cgls_update(int64_t n, int64_t m, Scalar
 // t; block 0 publishes the finished gamma_new.  Same arithmetic as trk_axpby(1, t, gamma_new/gamma_old, p).
 template <bool VEC>
 __global__ __launch_bounds__(NT) void k_cgls_p_update(int64_t n, const float* __restrict__ t, float* p, ScalarSrc gnew,
-                                                      const double* gold, double* pub_gamma, int nt) {
+                                                      const double* gold, double* pub_gamma) {
   __shared__ double bc;
   if (threadIdx.x < 64) {
     const double g = scalar_from_wave(gnew, threadIdx.x);
@@ -400,7 +392,7 @@ __global__ __launch_bounds__(NT) void k_cgls_p_update(int64_t n, const float* __
       o.y = fmaf(1.f, v.y, b * w.y);
       o.z = fmaf(1.f, v.z, b * w.z);
       o.w = fmaf(1.f, v.w, b * w.w);
-      if (nt & 8) st4_nt(p, i, o); else st4(p, i, o);
+      st4(p, i, o);
     }
   }
   for (int64_t i = tail0 + tid; i < n; i += nth) p[i] = fmaf(1.f, t[i], b * p[i]);
@@ -410,7 +402,7 @@ __global__ __launch_bounds__(NT) void k_cgls_p_update(int64_t n, const float* __
 // r -= (gamma_old / S(delta)) w with delta possibly still the block partials of the forward kernel; block 0 publishes it.
 template <bool VEC>
 __global__ __launch_bounds__(NT) void k_cgls_r_update(int64_t m, const double* gold, ScalarSrc delta, float* r,
-                                                      const float* __restrict__ w, double* pub_delta, int nt) {
+                                                      const float* __restrict__ w, double* pub_delta) {
   __shared__ double bc;
   if (threadIdx.x < 64) {
     const double d = scalar_from_wave(delta, threadIdx.x);
@@ -426,15 +418,14 @@ __global__ __launch_bounds__(NT) void k_cgls_r_update(int64_t m, const double* g
   if (VEC) {
     const int64_t m4 = m >> 2;
     tail0 = m4 << 2;
-    for (int64_t i0 = tid; i0 < m4; i0 += nth) {
-      const int64_t i = (nt & 256) ? m4 - 1 - i0 : i0;      // TRK_REV: last-written rows of the producer first (Infinity-Cache experiment)
+    for (int64_t i = tid; i < m4; i += nth) {
       float4 rv = ld4(r, i);
       const float4 wv = ld4(w, i);
       rv.x = fmaf(-step, wv.x, rv.x);
       rv.y = fmaf(-step, wv.y, rv.y);
       rv.z = fmaf(-step, wv.z, rv.z);
       rv.w = fmaf(-step, wv.w, rv.w);
-      if (nt & 4) st4_nt(r, i, rv); else st4(r, i, rv);
+      st4(r, i, rv);
     }
   }
   for (int64_t i = tail0 + tid; i < m; i += nth) r[i] = fmaf(-step, w[i], r[i]);
@@ -463,8 +454,7 @@ __global__ __launch_bounds__(NT) void k_cgls_xp_update(int64_t n, const double* 
   double s0 = 0.0, s1 = 0.0, s2 = 0.0;
   const int64_t tid = (int64_t)blockIdx.x * NT + threadIdx.x, nth = (int64_t)gridDim.x * NT;
   const int64_t n4 = n >> 2;
-  for (int64_t i0 = tid; i0 < n4; i0 += nth) {
-    const int64_t i = (nt & 256) ? n4 - 1 - i0 : i0;        // TRK_REV (see k_cgls_r_update)
+  for (int64_t i = tid; i < n4; i += nth) {
     const float4 xv = (nt & 16) ? ld4_nt(x, i) : ld4(x, i), pv = ld4(p, i), tv = (nt & 32) ? ld4_nt(t, i) : ld4(t, i);
     const float4 d = make_float4(step * pv.x, step * pv.y, step * pv.z, step * pv.w);
     const float4 xn = make_float4(xv.x + d.x, xv.y + d.y, xv.z + d.z, xv.w + d.w);
@@ -474,7 +464,7 @@ __global__ __launch_bounds__(NT) void k_cgls_xp_update(int64_t n, const double* 
     o.y = fmaf(1.f, tv.y, b * pv.y);
     o.z = fmaf(1.f, tv.z, b * pv.z);
     o.w = fmaf(1.f, tv.w, b * pv.w);
-    if (nt & 8) st4_nt(p, i, o); else st4(p, i, o);
+    st4(p, i, o);
     s0 += (double)xn.x * xn.x + (double)xn.y * xn.y + (double)xn.z * xn.z + (double)xn.w * xn.w;
     s1 += (double)d.x * d.x + (double)d.y * d.y + (double)d.z * d.z + (double)d.w * d.w;
     if (HAS_XT) {
@@ -788,7 +778,7 @@ struct YArg {
   }
 };
 
-template <bool HAS_BASE, bool SUMSQ, bool VEC, bool HAS_REF = false, int U = 8, class YS = YPtr>
+template <bool HAS_BASE, bool SUMSQ, bool VEC, bool HAS_REF = false, class YS = YPtr>
 __global__ __launch_bounds__(NT) void k_gemv_n(const YS y, const float* __restrict__ V, int64_t ld, int k, int64_t n,
                                                double a, const float* base, double sc,
                                                float* out, double* __restrict__ partials,
@@ -812,8 +802,8 @@ __global__ __launch_bounds__(NT) void k_gemv_n(const YS y, const float* __restri
         o2 = a * b.z;
         o3 = a * b.w;
       }
-      // rows of the basis are requested in groups — U, then 8, then 4 — before the first of a group is used (the compiler's own
-      // unrolling of the plain loop kept 4 in flight; U is the launcher's choice, trk_gemv_n)
+      // rows of the basis are requested in groups — 8, then 4 — before the first of a group is used (the compiler's own unrolling
+      // of the plain loop kept 4 in flight; measured, tools/gemv_micro.py: 4 -> 5.4-5.8 TB/s, 8 (+ 8 workgroups per CU) -> 6.2-6.4)
       int j = 0;
       auto group = [&](auto width) {
         constexpr int W = decltype(width)::value;
@@ -830,9 +820,8 @@ __global__ __launch_bounds__(NT) void k_gemv_n(const YS y, const float* __restri
         }
         j += W;
       };
-      while (j + U <= k) group(std::integral_constant<int, U>{});
-      if (U > 8 && j + 8 <= k) group(std::integral_constant<int, 8>{});
-      if (U > 4 && j + 4 <= k) group(std::integral_constant<int, 4>{});
+      while (j + 8 <= k) group(std::integral_constant<int, 8>{});
+      if (j + 4 <= k) group(std::integral_constant<int, 4>{});
       while (j < k) group(std::integral_constant<int, 1>{});
       float4 o = make_float4((float)o0, (float)o1, (float)o2, (float)o3);
       st4(out, i, o);
@@ -927,8 +916,7 @@ __global__ __launch_bounds__(NT) void k_gemv_n_split(const double* __restrict__ 
 }
 // whether the short-vector form serves a call (no fused norm, aligned, few columns, enough rows to be worth splitting)
 static bool gemv_n_split_serves(int64_t n, int k, bool vec) {
-  static const int on = env_int("TRK_GEMVN_SPLIT", 1);
-  return on && vec && (n % 4) == 0 && n > 0 && (n >> 2) <= (int64_t)64 * 4 * cu_count() && k >= 12 && k <= KMAX_LDS;
+  return vec && (n % 4) == 0 && n > 0 && (n >> 2) <= (int64_t)64 * 4 * cu_count() && k >= 12 && k <= KMAX_LDS;
 }
 
 // ------------------------------------------------------------------ the new basis vector AND the next iterate in ONE pass over the basis
@@ -942,7 +930,7 @@ static bool gemv_n_split_serves(int64_t n, int k, bool vec) {
 //   x  = sum_{j<k} y[j] V[j] + y[k] vn              — k_gemv_n's sum over the k + 1 stored vectors, term for term (vn as stored)
 // HAS_REF: block partials of ||x - ref||^2 (trk_gemv_n_err's); chk != nullptr: block partials of ||w - V c||^2 as computed (float64,
 // before the scaling) — what rho^2 stands for, for callers who want to see the two agree.
-template <bool VEC, bool HAS_X, bool HAS_REF, int U>
+template <bool VEC, bool HAS_X, bool HAS_REF>
 __global__ __launch_bounds__(NT) void k_gemv_orth_iter(const float* __restrict__ V, int64_t ld, int k, int64_t n,
                                                        const float* __restrict__ w, const double* __restrict__ c,
                                                        const double* __restrict__ rho2, const double* __restrict__ y, float* vn, float* x,
@@ -986,8 +974,8 @@ __global__ __launch_bounds__(NT) void k_gemv_orth_iter(const float* __restrict__
         }
         j += W;
       };
-      while (j + U <= k) group(std::integral_constant<int, U>{});
-      if (U > 4 && j + 4 <= k) group(std::integral_constant<int, 4>{});
+      while (j + 8 <= k) group(std::integral_constant<int, 8>{});
+      if (j + 4 <= k) group(std::integral_constant<int, 4>{});
       while (j < k) group(std::integral_constant<int, 1>{});
       if (chk) accc += (o0 * o0 + o1 * o1) + (o2 * o2 + o3 * o3);
       const float4 vo = make_float4((float)(o0 * inv), (float)(o1 * inv), (float)(o2 * inv), (float)(o3 * inv));
@@ -1281,94 +1269,6 @@ __global__ __launch_bounds__(NT) void k_wgram(const float* __restrict__ W, int64
     }
 }
 
-// ------------------------------------------------------------------ weighted Gram, LDS-staged (every row read once)
-// Rows of the augmented matrix  [ w*W_0 ; ... ; w*W_{k-1} ; b ; w*b ]  for a chunk of CH elements are staged in LDS (fp32),
-// then every thread owns one 4x4 tile of row pairs (upper triangle) and a residue class of the chunk's elements and
-// accumulates 16 fp64 FMAs per element.  One pass gives G = W diag(w^2) W^T, c1 = W (w*b), c2 = W (w^2*b) and ||w*b||^2.
-// HBM traffic 4*m*(k+2) bytes; LDS rows are padded by one float (row stride CH+1) so that the 8 row reads of a wave's
-// different tiles fall on different banks.  Partials: [block][KA*KA] (KA = k + 2 when b is given).
-constexpr int WG_TILE = 4;
-
-template <bool HAS_W, bool HAS_B>
-__global__ __launch_bounds__(NT) void k_wgram2(const float* __restrict__ W, int64_t ld, int k, int64_t m,
-                                               const float* __restrict__ w, const float* __restrict__ bvec, int CH,
-                                               double* __restrict__ partials) {
-  extern __shared__ float smem[];
-  const int KA = k + (HAS_B ? 2 : 0);
-  const int nt = (KA + WG_TILE - 1) / WG_TILE, KP = nt * WG_TILE;
-  const int ntu = nt * (nt + 1) / 2;
-  const int RS = CH + 1;                                  // padded row stride (floats)
-  const int nslice = NT / ntu;                            // >= 1 (host guarantees ntu <= NT)
-  const int pair = threadIdx.x % ntu, slice = threadIdx.x / ntu;
-  const bool worker = slice < nslice;
-  int ta = 0, rem = pair;
-  while (rem >= nt - ta) {
-    rem -= nt - ta;
-    ++ta;
-  }
-  const int a0 = ta * WG_TILE, b0 = (ta + rem) * WG_TILE;
-  double acc[WG_TILE][WG_TILE];
-#pragma unroll
-  for (int a = 0; a < WG_TILE; ++a)
-#pragma unroll
-    for (int b = 0; b < WG_TILE; ++b) acc[a][b] = 0.0;
-
-  const int64_t nchunk = (m + CH - 1) / CH;
-  for (int64_t c = blockIdx.x; c < nchunk; c += gridDim.x) {
-    const int64_t e0 = c * CH;
-    const int len = (int)((m - e0 < CH) ? (m - e0) : CH);
-    // stage: row r, element e  ->  smem[r*RS + e]
-    for (int idx = threadIdx.x; idx < KP * CH; idx += NT) {
-      const int r = idx / CH, e = idx - r * CH;
-      float v = 0.f;
-      if (e < len && r < KA) {
-        const float wv = HAS_W ? w[e0 + e] : 1.f;
-        if (r < k) v = W[(int64_t)r * ld + e0 + e] * wv;
-        else if (r == k) v = bvec[e0 + e];
-        else v = bvec[e0 + e] * wv;
-      }
-      smem[r * RS + e] = v;
-    }
-    __syncthreads();
-    if (worker) {
-      for (int e = slice; e < len; e += nslice) {
-        double av[WG_TILE], bw[WG_TILE];
-#pragma unroll
-        for (int a = 0; a < WG_TILE; ++a) av[a] = (double)smem[(a0 + a) * RS + e];
-#pragma unroll
-        for (int b = 0; b < WG_TILE; ++b) bw[b] = (double)smem[(b0 + b) * RS + e];
-#pragma unroll
-        for (int a = 0; a < WG_TILE; ++a)
-#pragma unroll
-          for (int b = 0; b < WG_TILE; ++b) acc[a][b] = fma(av[a], bw[b], acc[a][b]);
-      }
-    }
-    __syncthreads();
-  }
-  // reduce the slices of each tile pair in a fixed order through LDS (reusing the staging area), then write the block partial
-  double* red = reinterpret_cast<double*>(smem);          // [NT][16]
-#pragma unroll
-  for (int a = 0; a < WG_TILE; ++a)
-#pragma unroll
-    for (int b = 0; b < WG_TILE; ++b) red[threadIdx.x * 16 + a * WG_TILE + b] = worker ? acc[a][b] : 0.0;
-  __syncthreads();
-  double* __restrict__ out = partials + (size_t)blockIdx.x * KA * KA;
-  for (int idx = threadIdx.x; idx < ntu * 16; idx += NT) {
-    const int pr = idx / 16, q = idx - pr * 16;
-    double t = 0.0;
-    for (int sl = 0; sl < nslice; ++sl) t += red[(sl * ntu + pr) * 16 + q];
-    int pta = 0, prem = pr;
-    while (prem >= nt - pta) {
-      prem -= nt - pta;
-      ++pta;
-    }
-    const int ra = pta * WG_TILE + q / WG_TILE, rb = (pta + prem) * WG_TILE + (q % WG_TILE);
-    if (ra < KA && rb < KA) {
-      out[(size_t)ra * KA + rb] = t;
-      out[(size_t)rb * KA + ra] = t;
-    }
-  }
-}
 
 // ------------------------------------------------------------------ weighted Gram on the matrix cores
 // The one GEMM-shaped contraction of the path (SYRK: G = R R^T, R = the <= 64 augmented rows, m up to 3e7 long) runs on
@@ -1657,12 +1557,11 @@ struct TvRow {
 // direction where eight v_mfma_f32_16x16x4_f32 took 256 — the fp32 matrix pipe, at the vector unit's own rate, was this kernel's
 // bound at two tiles (k = 17 .. 32: 0.51-0.57 ms whatever k; 48 MFMAs x 32 cycles per 32 pixels), now the rows' traffic is.
 // The verdict of trk_wgram_tv's 'auto' arithmetic (the probe is further down: k_wgram_tv_probe): sums = the probe's 2 x 10 finished
-// sums {S_ab, S'_ab}; worst = max_ab |S' - S| / sqrt(S_aa S_bb); verdict = worst > threshold.  Every workgroup of the pair of Gram
-// launches evaluates it (20 scalar loads, the same bits everywhere); the first one of the bf16 launch also records it in `record`.
+// sums {S_ab, S'_ab}; worst = max_ab |S' - S| / sqrt(S_aa S_bb); verdict = worst > threshold.  Every workgroup of the Gram launch
+// evaluates it (20 scalar loads, the same bits everywhere); the first one also records it in `record`.
 struct ProbeGate {
-  const double* sums;     // NULL: no gating
+  const double* sums;     // NULL: no probe ('auto' not chosen)
   double threshold;
-  int want;               // this launch runs iff verdict == want
   double* record;         // {verdict, worst} for trk_wgram_tv_last_probe
   int groups = 1;         // sets of four sampled basis vectors: 2 x 10 sums each (k_wgram_tv_probe)
 };
@@ -1683,7 +1582,7 @@ __device__ __forceinline__ int probe_verdict(const ProbeGate& pg, bool record) {
       }
   }
   const int verdict = worst > pg.threshold ? 1 : 0;
-  if (record && pg.want == 0 && pg.record) {
+  if (record && pg.record) {
     pg.record[0] = (double)verdict;
     pg.record[1] = worst;
   }
@@ -1813,23 +1712,19 @@ __device__ __forceinline__ void tv_row_products(const float4 (&Px)[T][2], const 
       for (int q = 0; q < 4; ++q) accd[p2][q] += (double)acc[p2][q];
 }
 
-template <int T, bool Z, int D, int BF = 3, int MINB = (D > 3 ? 1 : T == 1 ? 4 : (T == 2 && !Z) ? 3 : 2)>
+// MINB: two tiles, three pieces: 256 registers (no spills) at 2 workgroups per CU is the faster form (532 / 605 us at k = 17 / 32
+// against 648 / 781 with 32 spilled registers at 3: profiles/r05/wgram_tv_pieces.txt)
+template <int T, bool Z, int D, int BF = 3, int MINB = (D > 3 ? 1 : T == 1 ? 4 : (T == 2 && !Z && BF != 3) ? 3 : 2)>
 __global__ __launch_bounds__(NT, MINB) void k_wgram_tv(const float* __restrict__ V, int64_t ld, int k, int N,
                                                     const float* __restrict__ w, int nbands, int band_rows,
-                                                    double* __restrict__ partials, const float* __restrict__ z, int lockstep_in,
+                                                    double* __restrict__ partials, const float* __restrict__ z, int lockstep,
                                                     ProbeGate pg) {
-  // 'auto' arithmetic (trk_wgram_tv_precision): the launch is one of a pair — two bf16 pieces / the fp32 pipe — of which the probe's
-  // verdict (worked out by every workgroup from the probe's 20 finished sums: no launch for it) lets exactly one run; the other leaves at once
-  // BF == 4: ONE launch holds both arithmetics and the verdict picks per launch (uniform branch in the step) — no idle launches
+  // 'auto' arithmetic (trk_wgram_tv_precision), BF == 4: ONE launch holds both arithmetics — two bf16 pieces / the fp32 pipe — and
+  // the probe's verdict (worked out by every workgroup from the probe's 20 finished sums: no launch for it) picks per launch
+  // (uniform branch in the step)
   bool use_f32 = false;
-  if constexpr (BF == 4) {
-    use_f32 = pg.sums && probe_verdict(pg, blockIdx.x == 0 && threadIdx.x == 0) != 0;
-  } else {
-    if (pg.sums && probe_verdict(pg, blockIdx.x == 0 && threadIdx.x == 0) != pg.want) return;
-  }
+  if constexpr (BF == 4) use_f32 = pg.sums && probe_verdict(pg, blockIdx.x == 0 && threadIdx.x == 0) != 0;
   constexpr int NP = T * (T + 1) / 2;
-  const int lockstep = lockstep_in & 1;
-  const bool no_xcd_map = (lockstep_in & 2) != 0;                // TRK_WGRAM_TV_NO_XCD=1: the round-robin unit order (A/B)
   __shared__ double red[3][4][64];
   __shared__ __attribute__((aligned(16))) float wl[NT / 64][Z ? 96 : 64];
   // lockstep (the launcher's choice when the workgroup's four waves always own four neighbouring strips of one band): the pixel
@@ -1869,7 +1764,7 @@ __global__ __launch_bounds__(NT, MINB) void k_wgram_tv(const float* __restrict__
   // so each XCD is given a CONTIGUOUS eighth of every band's strip groups: the neighbour line is then in its own L2 except at the
   // eight seams.  Needs the groups of a band to divide by 8 (N a multiple of 1024) and a grid that is a multiple of 8.
   const int groups = strips / (NT / 64);
-  const bool xcd_map = strips % (NT / 64) == 0 && (groups & 7) == 0 && (gridDim.x & 7) == 0 && !no_xcd_map;   // (uniform)
+  const bool xcd_map = strips % (NT / 64) == 0 && (groups & 7) == 0 && (gridDim.x & 7) == 0;   // (uniform)
   // The whole sweep once per arithmetic AR (0 fp32 pipe, 2 / 3 bf16 pieces).  BF == 4 ('auto') instantiates it twice under ONE uniform
   // branch on the probe's verdict: both forms in one launch, each with its own register allocation (a branch inside the step made
   // the allocator keep both forms' operands live: 34-99 spilled registers).
@@ -2099,14 +1994,10 @@ struct LwRow {
 template <int T, bool Z, int BF>
 __global__ __launch_bounds__(LW_NT, T == 1 ? 4 : 2) void k_wgram_tv_lds(const float* __restrict__ V, int64_t ld, int k, int N,
                                                            const float* __restrict__ w, int nbands, int band_rows,
-                                                           double* __restrict__ partials, const float* __restrict__ z, int flags,
+                                                           double* __restrict__ partials, const float* __restrict__ z,
                                                            ProbeGate pg) {
   bool use_f32 = false;
-  if constexpr (BF == 4) {
-    use_f32 = pg.sums && probe_verdict(pg, blockIdx.x == 0 && threadIdx.x == 0) != 0;
-  } else {
-    if (pg.sums && probe_verdict(pg, blockIdx.x == 0 && threadIdx.x == 0) != pg.want) return;
-  }
+  if constexpr (BF == 4) use_f32 = pg.sums && probe_verdict(pg, blockIdx.x == 0 && threadIdx.x == 0) != 0;
   constexpr int NP = T * (T + 1) / 2, NV = 16 * T, SF = NV * LW_RS + LW_XF;
   __shared__ __attribute__((aligned(16))) float smem[LW_S * SF];                  // (ALL of the kernel's LDS: the sums at the end alias it)
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63, r = lane & 15, sl = lane >> 4;
@@ -2134,7 +2025,7 @@ __global__ __launch_bounds__(LW_NT, T == 1 ? 4 : 2) void k_wgram_tv_lds(const fl
   for (int t = 0; t < T; ++t) accz[t] = 0.0;
   const int tiles = N / LW_COLS;
   const int64_t units = (int64_t)tiles * nbands;
-  const bool xcd_map = (tiles & 7) == 0 && (gridDim.x & 7) == 0 && (flags & 2) == 0;      // (uniform) as in k_wgram_tv: an XCD's tiles are neighbours
+  const bool xcd_map = (tiles & 7) == 0 && (gridDim.x & 7) == 0;      // (uniform) as in k_wgram_tv: an XCD's tiles are neighbours
   __syncthreads();
 
   auto run = [&](auto arith_tag) {
@@ -2403,28 +2294,6 @@ __global__ __launch_bounds__(NT) void k_wgram_tv_probe(const float* __restrict__
   const double t = block_sum_many<NT, 2 * PROBE_P>(acc, lds);
   if (threadIdx.x < 2 * PROBE_P) part[((size_t)blockIdx.x * gridDim.y + blockIdx.y) * 2 * PROBE_P + threadIdx.x] = t;
 }
-// k_finalize / k_finalize_split of core.hip for one launch of such a pair (outputs from nsplit on go to out2)
-__global__ __launch_bounds__(256) void k_finalize_gated(const double* __restrict__ partials, int nblocks, int stride, double* __restrict__ out,
-                                                        int nsplit, double* __restrict__ out2, ProbeGate pg) {
-  if (probe_verdict(pg, false) != pg.want) return;
-  __shared__ double lds[4];
-  const int o = blockIdx.x;
-  const double* __restrict__ p = partials + o;
-  double v0 = 0.0, v1 = 0.0, v2 = 0.0, v3 = 0.0;
-  int b = threadIdx.x;
-  for (; b + 768 < nblocks; b += 1024) {
-    v0 += p[(size_t)b * stride];
-    v1 += p[(size_t)(b + 256) * stride];
-    v2 += p[(size_t)(b + 512) * stride];
-    v3 += p[(size_t)(b + 768) * stride];
-  }
-  for (; b < nblocks; b += 256) v0 += p[(size_t)b * stride];
-  const double v = block_sum<256>((v0 + v1) + (v2 + v3), lds);
-  if (threadIdx.x == 0) {
-    if (o < nsplit) out[o] = v;
-    else out2[o - nsplit] = v;
-  }
-}
 
 // scatter the augmented Gram [KA x KA] into G (k x k), c1, c2 (and optionally ||w b||^2)
 __global__ void k_wgram_unpack(const double* __restrict__ Ga, int k, int KA, double* __restrict__ G, double* __restrict__ c1,
@@ -2611,9 +2480,9 @@ int trk_cgls_r_update(int64_t m, const double* gamma_old, const double* delta, i
   const ScalarSrc d{delta, delta_n};
   hipStream_t s = (hipStream_t)st;
   if (aligned16(r) && aligned16(w))
-    hipLaunchKernelGGL((k_cgls_r_update<true>), dim3(grid), dim3(NT), 0, s, m, gamma_old, d, r, w, publish_delta, stream_nontemporal(m));
+    hipLaunchKernelGGL((k_cgls_r_update<true>), dim3(grid), dim3(NT), 0, s, m, gamma_old, d, r, w, publish_delta);
   else
-    hipLaunchKernelGGL((k_cgls_r_update<false>), dim3(grid), dim3(NT), 0, s, m, gamma_old, d, r, w, publish_delta, stream_nontemporal(m));
+    hipLaunchKernelGGL((k_cgls_r_update<false>), dim3(grid), dim3(NT), 0, s, m, gamma_old, d, r, w, publish_delta);
   TRK_LAUNCH_CHECK();
   return TRK_OK;
 }
@@ -2645,9 +2514,9 @@ int trk_cgls_p_update(int64_t n, const float* t, float* p, const double* gamma_n
   const ScalarSrc g{gamma_new, gamma_new_n};
   hipStream_t s = (hipStream_t)st;
   if (aligned16(t) && aligned16(p))
-    hipLaunchKernelGGL((k_cgls_p_update<true>), dim3(grid), dim3(NT), 0, s, n, t, p, g, gamma_old, publish_gamma, stream_nontemporal(n));
+    hipLaunchKernelGGL((k_cgls_p_update<true>), dim3(grid), dim3(NT), 0, s, n, t, p, g, gamma_old, publish_gamma);
   else
-    hipLaunchKernelGGL((k_cgls_p_update<false>), dim3(grid), dim3(NT), 0, s, n, t, p, g, gamma_old, publish_gamma, stream_nontemporal(n));
+    hipLaunchKernelGGL((k_cgls_p_update<false>), dim3(grid), dim3(NT), 0, s, n, t, p, g, gamma_old, publish_gamma);
   TRK_LAUNCH_CHECK();
   return TRK_OK;
 }
@@ -2769,17 +2638,11 @@ int trk::gemv_n_partials(const float* V, int64_t ld, int k, int64_t n, const dou
     *nblk = 0;
     return TRK_OK;
   }
-  static const int U = env_int("TRK_GEMVN_UNROLL", 8);        // measured, tools/gemv_micro.py: 4 -> 5.4-5.8 TB/s, 8 (+ 8 blocks per CU) -> 6.2-6.4
-  static const int gmul = env_int("TRK_GEMVN_GRID", 8);          // blocks per CU (0: stream_grid's 4)
-  const int grid_n = gmul > 0 ? (int)std::min<int64_t>((n + (int64_t)NT * 4 - 1) / ((int64_t)NT * 4), (int64_t)cu_count() * gmul) : grid;
+  // 8 workgroups per CU (tools/gemv_micro.py)
+  const int grid_n = (int)std::min<int64_t>((n + (int64_t)NT * 4 - 1) / ((int64_t)NT * 4), (int64_t)cu_count() * 8);
   if (sumsq)                                                     // one partial per workgroup of the grid actually launched
     if (int rc = scratch_doubles(s, (size_t)(grid_n > grid ? grid_n : grid), &part)) return rc;
-#define GN(HB, SS, VC)                                                                                                            \
-  do {                                                                                                                            \
-    if (U >= 16) hipLaunchKernelGGL((k_gemv_n<HB, SS, VC, false, 16>), dim3(grid_n), dim3(NT), 0, s, YPtr{y}, V, ld, k, n, a, base, sc, out, part, (const float*)nullptr, stream_nontemporal(n)); \
-    else if (U >= 8) hipLaunchKernelGGL((k_gemv_n<HB, SS, VC, false, 8>), dim3(grid_n), dim3(NT), 0, s, YPtr{y}, V, ld, k, n, a, base, sc, out, part, (const float*)nullptr, stream_nontemporal(n)); \
-    else hipLaunchKernelGGL((k_gemv_n<HB, SS, VC, false, 4>), dim3(grid_n), dim3(NT), 0, s, YPtr{y}, V, ld, k, n, a, base, sc, out, part, (const float*)nullptr, stream_nontemporal(n)); \
-  } while (0)
+#define GN(HB, SS, VC) hipLaunchKernelGGL((k_gemv_n<HB, SS, VC>), dim3(grid_n), dim3(NT), 0, s, YPtr{y}, V, ld, k, n, a, base, sc, out, part, (const float*)nullptr, stream_nontemporal(n))
   if (base) {
     if (sumsq) { if (vec) GN(true, true, true); else GN(true, true, false); }
     else       { if (vec) GN(true, false, true); else GN(true, false, false); }
@@ -2916,12 +2779,9 @@ int trk_gemv_n_err(const float* V, int64_t ld, int k, int64_t n, const double* y
   TRK_REQUIRE(V && y && out && ref && err_partials && n_blocks, "trk_gemv_n_err: NULL argument");
   TRK_REQUIRE(k >= 1 && k <= KMAX_LDS && n >= 0 && ld >= n, "trk_gemv_n_err: need 1 <= k <= %d, n >= 0, ld >= n", KMAX_LDS);
   // the launch shape of trk_gemv_n (8 workgroups per CU: tools/gemv_micro.py) when the caller's buffer has room for its partials
-  static const int gmul = env_int("TRK_GEMVN_GRID", 8);
   int grid = stream_grid(n);
-  if (gmul > 0) {
-    const int g8 = (int)std::min<int64_t>((n + (int64_t)NT * 4 - 1) / ((int64_t)NT * 4), (int64_t)cu_count() * gmul);
-    if (g8 >= 1 && g8 <= capacity_blocks) grid = g8;
-  }
+  const int g8 = (int)std::min<int64_t>((n + (int64_t)NT * 4 - 1) / ((int64_t)NT * 4), (int64_t)cu_count() * 8);
+  if (g8 >= 1 && g8 <= capacity_blocks) grid = g8;
   TRK_REQUIRE(grid <= capacity_blocks, "trk_gemv_n_err: partial buffer too small (%d blocks needed)", grid);
   *n_blocks = grid;
   hipStream_t s = (hipStream_t)st;
@@ -2942,12 +2802,9 @@ int trk_gemv_orth_iterate(const float* V, int64_t ld, int k, int64_t n, const fl
   TRK_REQUIRE(!ref || (x_next && err_partials && n_blocks), "trk_gemv_orth_iterate: ref needs x_next and room for the partials");
   TRK_REQUIRE(k >= 1 && k < KMAX_LDS && n >= 0 && ld >= n, "trk_gemv_orth_iterate: need 1 <= k < %d, n >= 0, ld >= n", KMAX_LDS);
   TRK_REQUIRE(vn != w && x_next != w && x_next != vn, "trk_gemv_orth_iterate: the outputs must not alias w or each other");
-  static const int gmul = env_int("TRK_GEMVN_GRID", 8);        // trk_gemv_n_err's launch shape
-  int grid = stream_grid(n);
-  if (gmul > 0) {
-    const int g8 = (int)std::min<int64_t>((n + (int64_t)NT * 4 - 1) / ((int64_t)NT * 4), (int64_t)cu_count() * gmul);
-    if (g8 >= 1 && (!ref || g8 <= capacity_blocks)) grid = g8;
-  }
+  int grid = stream_grid(n);                                     // trk_gemv_n_err's launch shape
+  const int g8 = (int)std::min<int64_t>((n + (int64_t)NT * 4 - 1) / ((int64_t)NT * 4), (int64_t)cu_count() * 8);
+  if (g8 >= 1 && (!ref || g8 <= capacity_blocks)) grid = g8;
   if (ref) {
     TRK_REQUIRE(grid <= capacity_blocks, "trk_gemv_orth_iterate: partial buffer too small (%d blocks needed)", grid);
     *n_blocks = grid;
@@ -2964,7 +2821,7 @@ int trk_gemv_orth_iterate(const float* V, int64_t ld, int k, int64_t n, const fl
     return TRK_OK;
   }
   const int nt = stream_nontemporal(n);
-#define GO(VC, HX, HR) hipLaunchKernelGGL((k_gemv_orth_iter<VC, HX, HR, 8>), dim3(grid), dim3(NT), 0, s, V, ld, k, n, w, c, rho2, y_next, vn, x_next, ref, err_partials, chk, nt)
+#define GO(VC, HX, HR) hipLaunchKernelGGL((k_gemv_orth_iter<VC, HX, HR>), dim3(grid), dim3(NT), 0, s, V, ld, k, n, w, c, rho2, y_next, vn, x_next, ref, err_partials, chk, nt)
   if (!x_next)  { if (vec) GO(true, false, false); else GO(false, false, false); }
   else if (ref) { if (vec) GO(true, true, true); else GO(false, true, true); }
   else          { if (vec) GO(true, true, false); else GO(false, true, false); }
@@ -2997,7 +2854,7 @@ int trk_gemv_n_hosty(const float* V, int64_t ld, int k, int64_t n, const double*
     const float* Vj = V + (int64_t)j0 * ld;
     const float* base = first ? nullptr : out;
     double* part = (last && ref) ? err_partials : nullptr;
-#define GH(HB, SS, VC, HR) hipLaunchKernelGGL((k_gemv_n<HB, SS, VC, HR, 8, YArg>), dim3(grid), dim3(NT), 0, s, ya, Vj, ld, kk, n, 1.0, base, 1.0, out, part, ref, 0)
+#define GH(HB, SS, VC, HR) hipLaunchKernelGGL((k_gemv_n<HB, SS, VC, HR, YArg>), dim3(grid), dim3(NT), 0, s, ya, Vj, ld, kk, n, 1.0, base, 1.0, out, part, ref, 0)
     if (first) {
       if (part) { if (vec) GH(false, true, true, true); else GH(false, true, false, true); }
       else      { if (vec) GH(false, false, true, false); else GH(false, false, false, false); }
@@ -3054,18 +2911,11 @@ int trk_gemv_nt(const float* V, int64_t ld, int k, int64_t n, const double* h, c
   return finalize_sums(part, bx, k, k, g, s);
 }
 
-static int g_wgram_tv_mode = -1;       // -1: not chosen yet (environment, else 1 = auto)
+static int g_wgram_tv_mode = 1;        // 1 auto, 0 fp32 pipe, 2 / 3 bf16 pieces (trk_wgram_tv_precision)
 static double* g_wgram_gate = nullptr; // {verdict, worst sampled deviation} of the last 'auto' call (device; process-wide like the mode)
-static int wgram_tv_mode() {
-  if (g_wgram_tv_mode < 0) {
-    const int pcs = env_int("TRK_WGRAM_TV_PIECES", 0);
-    g_wgram_tv_mode = env_int("TRK_WGRAM_TV_F32", 0) ? 0 : (pcs == 3 ? 3 : pcs == 2 ? 2 : 1);
-  }
-  return g_wgram_tv_mode;
-}
 int trk_wgram_tv_precision(int mode) {
   TRK_REQUIRE(mode >= -1 && mode <= 3, "trk_wgram_tv_precision: mode 1 (auto), 0 (fp32 pipe), 2 or 3 (bf16 pieces), -1 (query)");
-  const int was = wgram_tv_mode();
+  const int was = g_wgram_tv_mode;
   if (mode >= 0) g_wgram_tv_mode = mode;
   return was;
 }
@@ -3095,41 +2945,33 @@ static int wgram_tv_run(const float* V, int64_t ld, int k, int N, const float* w
               "trk_wgram_tv: need N a multiple of 32, 16-byte aligned rows and weights");
   hipStream_t s = (hipStream_t)st;
   const int T16 = (k + 15) / 16;
-  static const int pc_env = env_int("TRK_WGRAM_TV_PER_CU", 0);
   const int strips = N / 32;
   // The four waves of a workgroup in step (see the kernel: the right-neighbour column handed over through LDS instead of fetched
   // again — 25-40 % less HBM traffic, one barrier per image row): pays where the rows' traffic is the bound.  Measured at 4096^2
   // (tools/wgram_tv_micro.py; us, lockstep vs not): plain, two tiles k = 20 / 32: 507 / 620 vs 592 / 831; one tile k = 16: 308 vs
   // 366, k <= 10 equal; with the dots of _z (218 registers, two workgroups per CU at two tiles): k = 18 / 26 / 32: 640 / 649 / 676 vs
   // 598 / 666 / 791 — from k = 25 on.
-  static const int ls_env = env_int("TRK_WGRAM_TV_LOCKSTEP", -1);
   const bool ls_pays = T16 == 1 ? k >= 12 : T16 == 2 ? (z ? k >= 22 : true) : false;      // (round 5, two bf16 pieces, _z: k = 20 455 vs 464 us, k = 24 540 vs 478)
-  const int lock = (strips % (NT / 64) == 0 && (ls_env < 0 ? ls_pays : ls_env != 0)) ? 1 : 0;
+  const int lock = (strips % (NT / 64) == 0 && ls_pays) ? 1 : 0;
   // workgroups per CU: what the registers let be resident while the matrix pipe is the bound; without the lockstep exchange fewer
   // once the rows' traffic is (k = 32 plain: 762 / 744 / 683 us with 4 / 2 / 1 — more waves, more row streams open at once)
-  const int per_cu = pc_env > 0 ? pc_env
-                   : lock ? (z ? (T16 == 1 ? 3 : 2) : 3)
+  const int per_cu = lock ? (z ? (T16 == 1 ? 3 : 2) : 3)
                    : z ? (T16 == 1 ? 3 : T16 == 2 ? 2 : 2)
                        : (T16 == 1 ? (k <= 11 ? 4 : k <= 14 ? 2 : 1) : T16 == 2 ? (k <= 25 ? 3 : 1) : 2);
   int bx = cu_count() * per_cu;
   // (strip, band) units, band-major: the waves in flight together then work on a few neighbouring image rows of every basis vector
-  static const int band_env = env_int("TRK_WGRAM_TV_BAND", 64);
-  int band_rows = band_env < N ? (band_env > 0 ? band_env : 16) : N;
+  int band_rows = 64 < N ? 64 : N;
   int nbands = (N + band_rows - 1) / band_rows;
   const int64_t units = (int64_t)strips * nbands;
   if ((int64_t)bx * (NT / 64) > units) bx = (int)((units + NT / 64 - 1) / (NT / 64));
   // Large images, at most two tiles of vectors: the rows of V staged through LDS in full lines (k_wgram_tv_lds): 256-column tiles,
-  // one workgroup of 8 waves per CU (two at one tile of vectors).  TRK_WGRAM_TV_LDS=0: the register-fed kernel everywhere (A/B).
-  static const int lds_env = env_int("TRK_WGRAM_TV_LDS", 1);
-  static const int lds_band_env = env_int("TRK_WGRAM_TV_LDS_BAND", 64);
-  static const int lds_pc_env = env_int("TRK_WGRAM_TV_LDS_PER_CU", 0);
-  const bool use_lds = lds_env != 0 && T16 <= 2 && N % LW_COLS == 0 && N >= 2048;
+  // one workgroup of 8 waves per CU (two at one tile of vectors).
+  const bool use_lds = T16 <= 2 && N % LW_COLS == 0 && N >= 2048;
   if (use_lds) {
-    band_rows = lds_band_env >= 4 && lds_band_env < N ? lds_band_env : 64;
-    while (N % band_rows) band_rows >>= 1;                      // (N is a multiple of 256: a power of two <= 256 divides it)
+    band_rows = 64;                                             // (N is a multiple of 256)
     nbands = N / band_rows;
     const int64_t lunits = (int64_t)(N / LW_COLS) * nbands;
-    bx = cu_count() * (lds_pc_env > 0 ? (lds_pc_env > 2 ? 2 : lds_pc_env) : (T16 == 1 ? 2 : 1));
+    bx = cu_count() * (T16 == 1 ? 2 : 1);
     if (T16 == 2 && bx > cu_count()) bx = cu_count();
     if (bx > lunits) bx = (int)lunits;
   }
@@ -3138,74 +2980,52 @@ static int wgram_tv_run(const float* V, int64_t ld, int k, int N, const float* w
   if (int rc = scratch_doubles(s, (size_t)bx * nv + ((size_t)PROBE_ROWS + 1) * 2 * 2 * PROBE_P, &part)) return rc;
   double* probe_part = part + (size_t)bx * nv;
   double* probe_sums = probe_part + (size_t)PROBE_ROWS * 2 * 2 * PROBE_P;
-  static const int no_xcd = env_int("TRK_WGRAM_TV_NO_XCD", 0) ? 2 : 0;
-  // Which arithmetic forms the tile products (trk_wgram_tv_precision; environment TRK_WGRAM_TV_F32=1 / TRK_WGRAM_TV_PIECES=2|3 set the
-  // process default): 1 auto (default: two bf16 pieces unless the probe finds the data's roundings correlated, then the fp32 pipe),
-  // 0 fp32 matrix pipe, 2 two bf16 pieces, 3 three bf16 pieces
-  const int mode = wgram_tv_mode();
-  // two tiles, three pieces: 256 registers (no spills) at 2 workgroups per CU is the faster form (532 / 605 us at k = 17 / 32 against
-  // 648 / 781 with 32 spilled registers at 3: profiles/r05/wgram_tv_pieces.txt)
-  static const int occ2 = env_int("TRK_WGRAM_TV_OCC2", 1);
-  ProbeGate pg{nullptr, 0.0, 0, nullptr, 1};
+  // Which arithmetic forms the tile products (trk_wgram_tv_precision): 1 auto (default: two bf16 pieces unless the probe finds the
+  // data's roundings correlated, then the fp32 pipe), 0 fp32 matrix pipe, 2 two bf16 pieces, 3 three bf16 pieces
+  const int mode = g_wgram_tv_mode;
+  ProbeGate pg{nullptr, 0.0, nullptr, 1};
   if (mode == 1) {
     if (!g_wgram_gate) TRK_HIP(hipMalloc((void**)&g_wgram_gate, 2 * sizeof(double)));
     // verdict threshold on the SAMPLED deviation: a third of the 1e-6 the contract promises (the sample is an estimate)
-    static const double thr = getenv("TRK_WGRAM_TV_PROBE_THRESHOLD") ? atof(getenv("TRK_WGRAM_TV_PROBE_THRESHOLD")) : 3e-7;
+    const double thr = 3e-7;
     const int row_step = N / PROBE_ROWS > 0 ? N / PROBE_ROWS : 1;
     const int prows = (N + row_step - 1) / row_step < PROBE_ROWS ? (N + row_step - 1) / row_step : PROBE_ROWS;
     const int pgroups = k >= 2 * PROBE_V ? 2 : 1;
     hipLaunchKernelGGL(k_wgram_tv_probe, dim3(prows, pgroups), dim3(NT), 0, s, V, ld, k, N, w, row_step, probe_part);
     TRK_LAUNCH_CHECK();
     if (int rc = finalize_sums(probe_part, prows, pgroups * 2 * PROBE_P, pgroups * 2 * PROBE_P, probe_sums, s)) return rc;
-    pg = ProbeGate{probe_sums, thr, 0, g_wgram_gate, pgroups};
+    pg = ProbeGate{probe_sums, thr, g_wgram_gate, pgroups};
   }
-  // arith: 0 fp32 pipe, 2 / 3 bf16 pieces; want: with a probe, the launch runs iff the probe's verdict equals it
-#define WTV(TT, ZZ, ARITH, WANT)                                                                                                                      \
+  // arith: 4 'auto' (both forms in one launch, the probe's verdict picks), 0 fp32 pipe, 2 / 3 bf16 pieces
+  const int arith = mode == 1 ? 4 : mode;
+#define WTV(TT, ZZ)                                                                                                                                   \
   do {                                                                                                                                                \
-    if ((ARITH) == 4) hipLaunchKernelGGL((k_wgram_tv<TT, ZZ, 3, 4>), dim3(bx), dim3(NT), 0, s, V, ld, k, N, w, nbands, band_rows, part, z, lock | no_xcd, ProbeGate{pg.sums, pg.threshold, 0, pg.record, pg.groups}); \
-    else if ((ARITH) == 0) hipLaunchKernelGGL((k_wgram_tv<TT, ZZ, 3, 0>), dim3(bx), dim3(NT), 0, s, V, ld, k, N, w, nbands, band_rows, part, z, lock | no_xcd, ProbeGate{pg.sums, pg.threshold, WANT, pg.record, pg.groups}); \
-    else if ((ARITH) == 2) hipLaunchKernelGGL((k_wgram_tv<TT, ZZ, 3, 2>), dim3(bx), dim3(NT), 0, s, V, ld, k, N, w, nbands, band_rows, part, z, lock | no_xcd, ProbeGate{pg.sums, pg.threshold, WANT, pg.record, pg.groups}); \
-    else if (TT == 2 && !ZZ && occ2) hipLaunchKernelGGL((k_wgram_tv<TT, ZZ, 3, 3, 2>), dim3(bx), dim3(NT), 0, s, V, ld, k, N, w, nbands, band_rows, part, z, lock | no_xcd, ProbeGate{pg.sums, pg.threshold, WANT, pg.record, pg.groups}); \
-    else hipLaunchKernelGGL((k_wgram_tv<TT, ZZ, 3, 3>), dim3(bx), dim3(NT), 0, s, V, ld, k, N, w, nbands, band_rows, part, z, lock | no_xcd, ProbeGate{pg.sums, pg.threshold, WANT, pg.record, pg.groups});           \
+    if (arith == 4) hipLaunchKernelGGL((k_wgram_tv<TT, ZZ, 3, 4>), dim3(bx), dim3(NT), 0, s, V, ld, k, N, w, nbands, band_rows, part, z, lock, pg);  \
+    else if (arith == 0) hipLaunchKernelGGL((k_wgram_tv<TT, ZZ, 3, 0>), dim3(bx), dim3(NT), 0, s, V, ld, k, N, w, nbands, band_rows, part, z, lock, pg); \
+    else if (arith == 2) hipLaunchKernelGGL((k_wgram_tv<TT, ZZ, 3, 2>), dim3(bx), dim3(NT), 0, s, V, ld, k, N, w, nbands, band_rows, part, z, lock, pg); \
+    else hipLaunchKernelGGL((k_wgram_tv<TT, ZZ, 3, 3>), dim3(bx), dim3(NT), 0, s, V, ld, k, N, w, nbands, band_rows, part, z, lock, pg);             \
+  } while (0)
+#define WTVL1(TT, ZZ, BFV) hipLaunchKernelGGL((k_wgram_tv_lds<TT, ZZ, BFV>), dim3(bx), dim3(LW_NT), 0, s, V, ld, k, N, w, nbands, band_rows, part, z, pg)
+#define WTVL(TT, ZZ)                                             \
+  do {                                                           \
+    if (arith == 4) WTVL1(TT, ZZ, 4);                            \
+    else if (arith == 0) WTVL1(TT, ZZ, 0);                       \
+    else if (arith == 2) WTVL1(TT, ZZ, 2);                       \
+    else WTVL1(TT, ZZ, 3);                                       \
   } while (0)
   // one pass of the chosen arithmetic: the kernel and the sum of its block partials
-#define WTVL1(TT, ZZ, BFV, WANT) hipLaunchKernelGGL((k_wgram_tv_lds<TT, ZZ, BFV>), dim3(bx), dim3(LW_NT), 0, s, V, ld, k, N, w, nbands, band_rows, part, z, (int)no_xcd, ProbeGate{pg.sums, pg.threshold, WANT, pg.record, pg.groups})
-#define WTVL(TT, ZZ, ARITH, WANT)                                \
-  do {                                                           \
-    if ((ARITH) == 4) WTVL1(TT, ZZ, 4, 0);                       \
-    else if ((ARITH) == 0) WTVL1(TT, ZZ, 0, WANT);               \
-    else if ((ARITH) == 2) WTVL1(TT, ZZ, 2, WANT);               \
-    else WTVL1(TT, ZZ, 3, WANT);                                 \
-  } while (0)
-  auto pass = [&](int arith, int want) -> int {
-    const bool two_pass = z && T16 == 3;     // three tiles AND the dots do not fit the register file (108 spilled registers): the dots
-    if (use_lds) {
-      if (z) { if (T16 == 1) WTVL(1, true, arith, want); else WTVL(2, true, arith, want); }
-      else { if (T16 == 1) WTVL(1, false, arith, want); else WTVL(2, false, arith, want); }
-    } else
-    if (two_pass) WTV(3, false, arith, want);   // of 33 <= k <= 48 in a pass of their own, below
-    else if (z) { if (T16 == 1) WTV(1, true, arith, want); else WTV(2, true, arith, want); }
-    else { if (T16 == 1) WTV(1, false, arith, want); else if (T16 == 2) WTV(2, false, arith, want); else WTV(3, false, arith, want); }
-    TRK_LAUNCH_CHECK();
-    const int nout = two_pass ? k * k : nv;
-    if (pg.sums && arith != 4) {
-      hipLaunchKernelGGL(k_finalize_gated, dim3(nout), dim3(256), 0, s, part, bx, nout, G, k * k, h, ProbeGate{pg.sums, pg.threshold, want, nullptr, pg.groups});
-      TRK_LAUNCH_CHECK();
-      return TRK_OK;
-    }
-    if (z && !two_pass) return finalize_sums_split(part, bx, nv, nv, G, k * k, h, s);
-    return finalize_sums(part, bx, k * k, k * k, G, s);
-  };
-  static const int auto_pair = env_int("TRK_WGRAM_TV_AUTO_PAIR", 0);     // 1: the gated pair of launches instead of one launch with both forms (A/B)
-  if (mode == 1 && auto_pair) {
-    if (int rc = pass(2, 0)) return rc;
-    if (int rc = pass(0, 1)) return rc;
-  } else if (mode == 1) {
-    if (int rc = pass(4, 0)) return rc;
-  } else {
-    if (int rc = pass(mode, 0)) return rc;
-  }
-  if (z && T16 == 3) return launch_gemv_t(V, ld, k, (int64_t)N * N, z, nullptr, 0, h, s);
+  const bool two_pass = z && T16 == 3;     // three tiles AND the dots do not fit the register file (108 spilled registers): the dots
+  if (use_lds) {
+    if (z) { if (T16 == 1) WTVL(1, true); else WTVL(2, true); }
+    else { if (T16 == 1) WTVL(1, false); else WTVL(2, false); }
+  } else
+  if (two_pass) WTV(3, false);             // of 33 <= k <= 48 in a pass of their own, below
+  else if (z) { if (T16 == 1) WTV(1, true); else WTV(2, true); }
+  else { if (T16 == 1) WTV(1, false); else if (T16 == 2) WTV(2, false); else WTV(3, false); }
+  TRK_LAUNCH_CHECK();
+  if (z && !two_pass) return finalize_sums_split(part, bx, nv, nv, G, k * k, h, s);
+  if (int rc = finalize_sums(part, bx, k * k, k * k, G, s)) return rc;
+  if (two_pass) return launch_gemv_t(V, ld, k, (int64_t)N * N, z, nullptr, 0, h, s);
   return TRK_OK;
 }
 #undef WTV
@@ -3219,17 +3039,13 @@ int trk_wgram(const float* W, int64_t ld, int k, int64_t m, const float* w, cons
   TRK_REQUIRE(!b1 || (c1 && c2), "trk_wgram: b1 given but c1/c2 NULL");
   hipStream_t s = (hipStream_t)st;
   const int KA = k + (b1 ? 2 : 0);
-  const int nt2 = ceil_div(KA, WG_TILE), ntu = nt2 * (nt2 + 1) / 2;
-  static const bool no_mfma = getenv("TRK_WGRAM_NO_MFMA") != nullptr;
-  if (KA <= 64 && !no_mfma) {
+  if (KA <= 64) {
     // matrix-core single pass (every row read once)
-    static const bool no_direct = getenv("TRK_WGRAM_NO_DIRECT") != nullptr;
     const bool al16 = (ld % 4 == 0) && aligned16(W) && (!w || aligned16(w)) && (!b1 || aligned16(b1));
-    const bool direct = al16 && !no_direct && KA <= 48;   // T = 4 does not fit the register file: 49..64 rows stay on the 32x32 kernel
+    const bool direct = al16 && KA <= 48;   // T = 4 does not fit the register file: 49..64 rows stay on the 32x32 kernel
     const int T16 = (KA + 15) / 16;
     // blocks per CU = what the register budget of the variant lets be resident (8 / 4 / 2 waves per SIMD for T = 1 / 2 / 3)
-    static const int per_cu_env = getenv("TRK_WGRAM_PER_CU") ? atoi(getenv("TRK_WGRAM_PER_CU")) : 0;
-    const int per_cu = per_cu_env ? per_cu_env : direct ? (T16 == 1 ? 8 : T16 == 2 ? 4 : 2) : 3;
+    const int per_cu = direct ? (T16 == 1 ? 8 : T16 == 2 ? 4 : 2) : 3;
     int64_t nchunk = (m + 127) / 128;
     int bx = (int)(nchunk < (int64_t)cu_count() * per_cu ? (nchunk > 0 ? nchunk : 1) : (int64_t)cu_count() * per_cu);
     if (bx > 2 * kMaxPartialBlocks) bx = 2 * kMaxPartialBlocks;
@@ -3253,33 +3069,6 @@ int trk_wgram(const float* W, int64_t ld, int k, int64_t m, const float* w, cons
       else   { if (b1) WM(2, false, true); else WM(2, false, false); }
     }
 #undef WM
-    TRK_LAUNCH_CHECK();
-    if (int rc = finalize_sums(part, bx, KA * KA, KA * KA, Ga, s)) return rc;
-    hipLaunchKernelGGL(k_wgram_unpack, dim3(1), dim3(256), 0, s, Ga, k, KA, G, c1, c2);
-    TRK_LAUNCH_CHECK();
-    return TRK_OK;
-  }
-  // The LDS-staged single-pass kernel reads every row once but is instruction-bound (8 ds_read + 8 cvt per 16 fp64 FMAs):
-  // measured slower than the tile-pair kernel at 4096^2 (k = 3..33: 3.2 ms vs 1.7 ms average), so it is opt-in.
-  static const bool use_lds = getenv("TRK_WGRAM_LDS") != nullptr;
-  if (use_lds && ntu <= NT) {
-    // LDS-staged single pass
-    const int KP = nt2 * WG_TILE;
-    int CH = (KP <= 40) ? 256 : (KP <= 80) ? 128 : 64;
-    size_t lds = (size_t)KP * (CH + 1) * sizeof(float);
-    const size_t red = (size_t)NT * 16 * sizeof(double);
-    if (lds < red) lds = red;
-    int64_t nchunk = (m + CH - 1) / CH;
-    int bx = (int)(nchunk < (int64_t)cu_count() * 2 ? (nchunk > 0 ? nchunk : 1) : (int64_t)cu_count() * 2);
-    if (bx > kMaxPartialBlocks) bx = kMaxPartialBlocks;
-    double* part = nullptr;  // [bx][KA*KA] partials, then the finished augmented Gram
-    const size_t npart = (size_t)bx * KA * KA;
-    if (int rc = scratch_doubles(s, npart + (size_t)KA * KA, &part)) return rc;
-    double* Ga = part + npart;
-#define WG2(HW, HB) hipLaunchKernelGGL((k_wgram2<HW, HB>), dim3(bx), dim3(NT), lds, s, W, ld, k, m, w, b1, CH, part)
-    if (w) { if (b1) WG2(true, true); else WG2(true, false); }
-    else   { if (b1) WG2(false, true); else WG2(false, false); }
-#undef WG2
     TRK_LAUNCH_CHECK();
     if (int rc = finalize_sums(part, bx, KA * KA, KA * KA, Ga, s)) return rc;
     hipLaunchKernelGGL(k_wgram_unpack, dim3(1), dim3(256), 0, s, Ga, k, KA, G, c1, c2);

@@ -442,8 +442,8 @@ class GramSchmidtByGram:
     G simply says so.  "Equal" is exact-arithmetic algebra: sweeping literally, the later sweeps also project out the rounding
     error of the first fp32 subtraction, which the single r - V c here carries once.  Measured where that could matter most —
     Arnoldi on the 9 x 9 blur, 100 steps, h_{k+1,k} / ||A v_k|| down to 0.03: max |V^T V - I| 9.65e-8 this way, 9.71e-8 sweep by
-    sweep (tests/test_gpu_solvers.py::test_arnoldi_orthogonality_by_gram_vs_sweeps); `by_gram=False` / `gram_sweeps=False` select
-    the literal form.
+    sweep (tests/test_gpu_solvers.py::test_arnoldi_orthogonality_by_gram_vs_sweeps); ArnoldiState(by_gram=False) and
+    `orthogonalize` are the literal form.
 
     At 4096^2 a pass over k = 18 basis vectors is 1.2 GB: MMGKS goes from 4 (k > 16) / 3 to 2 passes per iteration for the
     sweeps, GKS from 6 / 4 to 2."""

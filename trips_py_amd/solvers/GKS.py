@@ -16,13 +16,9 @@ from .. import _trace
 from .._io import Formatter, History, as_operator
 from ..engine import Coef
 from ..decompositions import golub_kahan_device
-from ..krylov import DeviceBasis, GramSchmidtByGram, orthogonalize
+from ..krylov import DeviceBasis, GramSchmidtByGram
 from ..operators import is_identity
 from ._common import check_delta, choose_lambda, gram_factor, gram_gcv_host, project_rhs, tikhonov_lstsq, small_host_blas
-
-
-import os as _os
-_TVDOT = _os.environ.get("TRK_GKS_TVDOT", "1") != "0"       # r . L^T L r from the pass that forms L^T L r (trk_tv_grad_dot)
 
 
 class _HaloTrack:
@@ -239,10 +235,10 @@ class _ProjectedBases:
             extra.append(self.zA)
         if self.from_v_L:
             hk = {} if self.halo is None else {"halo": self.r_halo}
-            if self.tL is None and rr and hasattr(getattr(eng, "lib", None), "trk_tv_grad_dot_xsq") and _TVDOT:
+            if self.tL is None and rr and hasattr(getattr(eng, "lib", None), "trk_tv_grad_dot_xsq"):
                 self.L.tv_grad(r, None, None, 1.0, out=self.zL, dot_with=r, dot_out=S.ref(o + 1), xsq_out=S.ref(o + 3), **hk)
                 rr_done = True
-            elif self.tL is None and hasattr(getattr(eng, "lib", None), "trk_tv_grad_dot") and _TVDOT:
+            elif self.tL is None and hasattr(getattr(eng, "lib", None), "trk_tv_grad_dot"):
                 self.L.tv_grad(r, None, None, 1.0, out=self.zL, dot_with=r, dot_out=S.ref(o + 1), **hk)   # z_L = L^T L r and r . z_L, one pass
             else:
                 if self.tL is None:
@@ -333,18 +329,17 @@ def GKS(A, b, L, projection_dim=3, n_iter=50, regparam="gcv", x_true=None, **kwa
     # numeric regparam: the projected problem is solved on the device from device-resident Gram data (no host round trip per
     # iteration); the automatic selectors need the factors on the host
     on_dev = (not isinstance(regparam, str)) and hasattr(eng, "gram_tikhonov") and hasattr(eng, "cgs_coeffs") \
-        and (kmax <= eng.GRAM_TIKHONOV_MAX_K or kwargs.get("border_inverse", True)) and kwargs.get("device_solve", True)
+        and kwargs.get("device_solve", True)
     dA, dL = bool(getattr(A, "streaming", False)), bool(getattr(L, "streaming", False))
     from_v = hasattr(eng, "gemv_t2") and kwargs.get("gram_from_v", True)
     # an automatic regparam ('gcv', the reference's default, 'dp', 'l_curve'; late round 6): the Gram data is kept on the device all the same — its rows then come from the
     # orthogonalisation sweep's own pass over V (gram_rows_from_sweep) instead of two sweeps of their own — and the selector downloads it
-    # with one copy per iteration (kwarg device_gram)
+    # with one copy per iteration
     dev_gram = on_dev or (isinstance(regparam, str) and hasattr(eng, "gram_tikhonov") and hasattr(eng, "cgs_coeffs")
-                          and kwargs.get("device_solve", True) and kwargs.get("device_gram", True))
+                          and kwargs.get("device_solve", True))
     pb = _ProjectedBases(A, L, bv, gk.V, kmax, on_device=dev_gram, from_v_A=dA and from_v, from_v_L=dL and from_v)
     Hs = History(eng, kwargs.get("history", True), n_iter, n, "GKS xHistory")
     Y = eng.scalars(kmax)
-    H = eng.scalars(3 * kmax)
     E = eng.scalars(n_iter + 3)             # E[0] = ||x_true||^2, E[1] = ||b||^2, E[2+i] = ||x_i - x_true||^2
     R = eng.scalars(n_iter + 1)             # ||r_i||^2
     tm, tp, r, rb = eng.empty(m), eng.empty(L.shape[0]), eng.empty(n), eng.empty(n)
@@ -355,11 +350,11 @@ def GKS(A, b, L, projection_dim=3, n_iter=50, regparam="gcv", x_true=None, **kwa
     b2 = float(E.host(1, 2)[0])
 
     fusedL = dL and getattr(L, "fused_tv", False) and kwargs.get("fused_tv", True)
-    gs_gram = GramSchmidtByGram(eng, pb.V, kmax) if (hasattr(eng, "cgs_coeffs") and kwargs.get("gram_sweeps", True)) else None
+    gs_gram = GramSchmidtByGram(eng, pb.V, kmax)
     lams, lam, x_dev = [], None, None
-    Minv, k_inv = (eng.scalars(kmax * kmax) if (on_dev and kwargs.get("border_inverse", True)) else None), 0
+    Minv, k_inv = (eng.scalars(kmax * kmax) if on_dev else None), 0
     # ||x_i - x_true||^2 rides the pass that forms x_i = V y (trk_gemv_n_err) as raw block partials
-    err_fused = xt is not None and hasattr(eng, "gemv_n_err") and kwargs.get("fused_error_norm", True)
+    err_fused = xt is not None and hasattr(eng, "gemv_n_err")
     EP_CAP = 2048
     EP, n_ep = (eng.scalars(EP_CAP * max(1, n_iter)) if err_fused else None), 0
     # One pass over the basis for the new vector AND the next iterate (late round 6; kwarg fused_orth_iterate): the projected problem of
@@ -367,7 +362,7 @@ def GKS(A, b, L, projection_dim=3, n_iter=50, regparam="gcv", x_true=None, **kwa
     # BEFORE r - V c is formed, and that pass leaves x_{ii+1} = V y' as well (trk_gemv_orth_iterate): two passes over V per iteration
     # instead of three.  Device-resident Gram data whose rows come from the sweep (`merged` below); on ranks r . r travels with the sweep's
     # products (the all-reduce of ||r - V c||^2 is gone) and the new vector's boundary frames come from the residual's, as before.
-    early = (dev_gram and gs_gram is not None and pb.from_v_L and hasattr(eng, "gemv_orth_iterate") and hasattr(eng, "gram_row_from_sweep")
+    early = (dev_gram and pb.from_v_L and hasattr(eng, "gemv_orth_iterate") and hasattr(eng, "gram_row_from_sweep")
              and kmax < 1024 and kwargs.get("gram_rows_from_sweep", True) and kwargs.get("fused_orth_iterate", True))
     x_ready = False
 
@@ -382,7 +377,7 @@ def GKS(A, b, L, projection_dim=3, n_iter=50, regparam="gcv", x_true=None, **kwa
             k_inv = k
             return
         hGA, hGL, hc = pb.download_grams(k) if dev_gram else (pb.GA[:k, :k], pb.GL[:k, :k], pb.c[:k])
-        one = gram_gcv_host(hGA, hGL, hc, hc) if (regparam == "gcv" and kwargs.get("host_solve_in_c", True)) else None
+        one = gram_gcv_host(hGA, hGL, hc, hc) if regparam == "gcv" else None
         if one is not None:                   # the whole projected problem in one library call (trk_host_gram_gcv)
             lam, y = one
             lams.append(lam)
@@ -434,7 +429,7 @@ def GKS(A, b, L, projection_dim=3, n_iter=50, regparam="gcv", x_true=None, **kwa
             eng.axpby(1.0, r, float(lam), rb, r)
         _trace.mark("GKS: orthogonalise, new basis vector")
         vn = pb.V.next_slot()
-        merged = (dev_gram and gs_gram is not None and pb.from_v_L and hasattr(eng, "gram_row_from_sweep")
+        merged = (dev_gram and pb.from_v_L and hasattr(eng, "gram_row_from_sweep")
                   and gs_gram.in_G == k - 1 and kwargs.get("gram_rows_from_sweep", True))
         cc = None
         if merged and early:
@@ -483,10 +478,8 @@ def GKS(A, b, L, projection_dim=3, n_iter=50, regparam="gcv", x_true=None, **kwa
             n_extra = int(pb.from_v_A) + int(pb.from_v_L)
             off = (2 + n_extra) * k
             cc = gs_gram.sweep(k, r, 3, vn, sumsq=R.ref(ii), extra=pb.sweep_operands(r, scal=gs_gram.W, off=off), tail=3)
-        elif gs_gram is not None:
-            cc = gs_gram.sweep(k, r, 3, vn, sumsq=R.ref(ii))                         # (:86-88) three sweeps, ||r||^2 fused
         else:
-            orthogonalize(eng, pb.V, k, r, H, 0, passes=3, out=vn, sumsq=R.ref(ii))
+            cc = gs_gram.sweep(k, r, 3, vn, sumsq=R.ref(ii))                         # (:86-88) three sweeps, ||r||^2 fused
         eng.allreduce(R, ii, ii + 1)
         if merged:
             eng.scale(Coef(1.0, den=R.ref(ii), sqrt_den=True), vn, vn)               # vn = r/||r|| (:89-91)

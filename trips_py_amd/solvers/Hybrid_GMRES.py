@@ -14,9 +14,9 @@ from ._common import check_delta, choose_lambda, tikhonov_lstsq, small_host_blas
 # basis size from which Hybrid-GMRES's GCV goes through the bidiagonal form instead of the dense SVD (below it the SVD is the
 # cheaper call: 20 us at k = 10 against 25-60 us of ctypes and NumPy overhead around dgebrd)
 BIDIAG_FROM_K = 12
-# (the same threshold in the one-call-per-iteration loop, kwarg worker_from_k: the two routes evaluate one GCV function a rounding
-# apart, and below k ~ 10 its minimum can be flat enough for the two answers to differ visibly — 56 % at one iterate of the 512^2 blur
-# with worker_from_k=2 — so the reference's route, the SVD, keeps the small iterates)
+# (the same threshold in the one-call-per-iteration loop: the two routes evaluate one GCV function a rounding apart, and below
+# k ~ 10 its minimum can be flat enough for the two answers to differ visibly — 56 % at one iterate of the 512^2 blur with a
+# threshold of 2 — so the reference's route, the SVD, keeps the small iterates)
 WORKER_FROM_K = BIDIAG_FROM_K
 
 
@@ -37,7 +37,7 @@ def Hybrid_GMRES(A, b, n_iter, regparam="gcv", x_true=None, **kwargs):
     fmt = Formatter(b)
     xt = None if x_true is None else eng.to_vec(x_true, n)
 
-    ar = ArnoldiState(A, b, n_iter, by_gram=kwargs.get("gram_sweeps", True))
+    ar = ArnoldiState(A, b, n_iter)
     bv = eng.to_vec(b, m) if (isinstance(regparam, str) and regparam == "dp") else None
     Hs = History(eng, kwargs.get("history", True), max(1, n_iter), n, "Hybrid_GMRES xHistory")
     Y = eng.scalars(max(1, n_iter))
@@ -59,7 +59,7 @@ def Hybrid_GMRES(A, b, n_iter, regparam="gcv", x_true=None, **kwargs):
     # threads, with the caller's lambda instead of a search, and the device runs nothing but the Arnoldi steps and x = V y (the
     # ~8 us k_hess_tikhonov left every iteration's critical path: 17-18 k -> 20 k iterations/s on the 512^2 blur)
     c_ok = (kwargs.get("c_loop", True) and n_iter >= 2 and getattr(eng, "world", 1) == 1 and bool(getattr(A, "_h", None))
-            and _plain_handle_apply(A) and ar.by_gram and hasattr(eng, "cgs_coeffs") and hasattr(eng, "gemv_n_hosty")
+            and _plain_handle_apply(A) and hasattr(eng, "cgs_coeffs") and hasattr(eng, "gemv_n_hosty")
             and hasattr(getattr(eng, "lib", None), "trk_hgmres_create") and ar.V.data.stride(0) >= n
             and (xt is None or err_fused) and HessenbergBidiag.available())
     c_fixed = (c_ok and not isinstance(regparam, str) and float(regparam) >= 0.0 and kwargs.get("device_solve", True)
@@ -74,12 +74,11 @@ def Hybrid_GMRES(A, b, n_iter, regparam="gcv", x_true=None, **kwargs):
         Yall = eng.scalars(kmax * kmax)              # y of iteration ii in row ii
         for ii in range(n_iter):
             k = ar._enqueue()                        # Arnoldi step k = ii + 1: its coefficients sit in ar.S[1 .. 1+2k), ||w||^2 in S[0]
-            second = ar.S.ref(1 + k) if ar.gram is None else None          # sweep-by-sweep form: two coefficient sets
             lam = 0 if ii == 0 else regparam                                # (:55-56: the first projected problem is unregularised)
             lams.append(lam)
             # steps 1 (lam = 0) and 2 start the chain, every later step borders the inverse it inherits (same lam)
             mode = 2 if k <= 2 else (1 if lam > 0 else 0)
-            eng.hess_tikhonov(Hd.ref(0), kmax + 1, Gd.ref(0), Mi.ref(0), kmax, ar.S.ref(1), second, ar.S.ref(0), ar.beta0, k,
+            eng.hess_tikhonov(Hd.ref(0), kmax + 1, Gd.ref(0), Mi.ref(0), kmax, ar.S.ref(1), None, ar.S.ref(0), ar.beta0, k,
                               lam, mode, Yall.ref(ii * kmax))
             x_dev = Hs.row(ii)
             if err_fused:
@@ -126,7 +125,7 @@ def Hybrid_GMRES(A, b, n_iter, regparam="gcv", x_true=None, **kwargs):
             svd = (sv, Vh, qb)
         else:
             lam = regparam
-        if svd is not None and lam > 0 and kwargs.get("solve_by_svd", True):
+        if svd is not None and lam > 0:
             # the Tikhonov minimiser of (:76) from the SVD the selector needed anyway: y = V diag(s / (s^2 + lam)) U^T bhat — O(k^2)
             # where the stacked least-squares problem is another O(k^3) factorisation per iteration
             sv, Vh, qb = svd
@@ -228,18 +227,15 @@ def Hybrid_GMRES(A, b, n_iter, regparam="gcv", x_true=None, **kwargs):
                 hy = (H @ y).reshape(-1, 1)
                 form(ii, lam, y, float(np.linalg.norm(bhat.reshape(1, -1) - hy)))
                 return
-            if kwargs.get("solve_by_svd", True):
-                # the SVD discrepancy_principle() takes of H (discrepancy_principle.py:68-70), taken here so that the
-                # Tikhonov solve below can share it
-                from ..reg_param.discrepancy_principle import discrepancy_principle
-                Uf, sv, Vh = sla.svd(H)
-                extra = {key: kwargs[key] for key in ("eta", "explicitProj") if key in kwargs}
-                lam = discrepancy_principle(None, None, None, 0.0, delta=kwargs.get("delta"), L_is_identity=True,
-                                            spectrum=(sv, Uf.T @ np.array(Pk).reshape(-1, 1), (k + 1, k)), **extra)
-                svd = (sv, Vh, Uf[:, :k].T @ bhat)
-            else:
-                lam = choose_lambda("dp", None, None, None, 0.0, kwargs, L_is_identity=True, dp_A=H, dp_bproj=np.array(Pk))
-        if svd is not None and lam > 0 and kwargs.get("solve_by_svd", True):
+            # the SVD discrepancy_principle() takes of H (discrepancy_principle.py:68-70), taken here so that the Tikhonov solve
+            # below can share it
+            from ..reg_param.discrepancy_principle import discrepancy_principle
+            Uf, sv, Vh = sla.svd(H)
+            extra = {key: kwargs[key] for key in ("eta", "explicitProj") if key in kwargs}
+            lam = discrepancy_principle(None, None, None, 0.0, delta=kwargs.get("delta"), L_is_identity=True,
+                                        spectrum=(sv, Uf.T @ np.array(Pk).reshape(-1, 1), (k + 1, k)), **extra)
+            svd = (sv, Vh, Uf[:, :k].T @ bhat)
+        if svd is not None and lam > 0:
             sv, Vh, qb = svd
             y = Vh.T @ ((sv / (sv * sv + lam)) * qb)
         else:
@@ -306,8 +302,8 @@ def Hybrid_GMRES(A, b, n_iter, regparam="gcv", x_true=None, **kwargs):
         ar.gram = GramSchmidtByGram(eng, ar.V, ar.capacity + 1)          # (installs the Gram row of V[0])
         drv = ct.c_void_p()
         # worker threads: the projected problems of consecutive iterates side by side (each O(k^3): ~150 us at k = 60 against ~55 us
-        # of kernels per step on the 512^2 blur), collected in order — kwarg search_workers
-        nw = max(1, min(16, int(kwargs.get("search_workers", 2))))
+        # of kernels per step on the 512^2 blur), collected in order
+        nw = 2
         from .Hybrid_LSQR import _Searcher
         while len(more_searchers) < nw - 1:                              # (borrowed like the first one; handed back by the caller)
             more_searchers.append(_Searcher.borrow(lib))
@@ -332,7 +328,7 @@ def Hybrid_GMRES(A, b, n_iter, regparam="gcv", x_true=None, **kwargs):
             d_ii, d_lam, d_res, d_blk = ct.c_int(), ct.c_double(), ct.c_double(), ct.c_int()
             ref = xt.data_ptr() if xt is not None else None
             posted = []                                                  # iterates whose jobs the workers hold, oldest first
-            from_k = max(2, int(kwargs.get("worker_from_k", WORKER_FROM_K)))
+            from_k = WORKER_FROM_K
             if c_fixed:                                                  # a number: no search, no flat minimum — every iterate but the first
                 from_k = 2
                 _lib.check(lib.trk_hgmres_fixed_lambda(drv, float(regparam)), "trk_hgmres_fixed_lambda")
@@ -344,7 +340,7 @@ def Hybrid_GMRES(A, b, n_iter, regparam="gcv", x_true=None, **kwargs):
                 _lib.check(lib.trk_hgmres_dp(drv, bv.data_ptr(), float(P.host(0, 1)[0]), float((kwargs.get("eta", 1.01) * kwargs["delta"]) ** 2),
                                              0.0, ct.byref(bpp)), "trk_hgmres_dp")
                 bp = np.ctypeslib.as_array(bpp, shape=(n_iter + 2,))
-                from_k = max(2, int(kwargs.get("worker_from_k", BIDIAG_FROM_K)))   # (from 2: measured, no gain — the early iterates come back unassigned)
+                from_k = BIDIAG_FROM_K                   # (from 2: measured, no gain — the early iterates come back unassigned)
 
             _lib.check(lib.trk_hgmres_start(drv), "trk_hgmres_start")
 

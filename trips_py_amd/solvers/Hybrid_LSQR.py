@@ -11,9 +11,8 @@ import scipy.linalg as sla
 from .. import _trace
 from .._io import Formatter, History, as_operator
 from ..krylov import GKState
-from ..reg_param._bidiag import bidiag_svd_first_row, bidiag_svd_project
-from ..reg_param.discrepancy_principle import discrepancy_principle, discrepancy_principle_bidiag
-from ..reg_param.gcv import fminbound_gcv_diag, fminbound_gcv_bidiag
+from ..reg_param.discrepancy_principle import discrepancy_principle_bidiag
+from ..reg_param.gcv import fminbound_gcv_bidiag
 from ._common import check_delta, choose_lambda, small_host_blas
 
 
@@ -181,7 +180,7 @@ def Hybrid_LSQR(A, b, n_iter=100, regparam="gcv", x_true=None, **kwargs):
     # the ~100 us this loop spent per iteration at 512^2 x 180 — more than the device needs for an iteration's kernels.)
     searcher = None
     if (on_host and regparam in ("gcv", "dp") and kwargs.get("async_search", True) and hasattr(eng, "lib")
-            and not kwargs.get("gcv_by_svd", False) and not kwargs.get("dp_by_svd", False) and n_iter > 2):
+            and n_iter > 2):
         searcher = _Searcher.borrow(eng.lib)
     waiting = None                           # the step whose lambda the worker is looking for
     clean = False
@@ -343,11 +342,7 @@ def Hybrid_LSQR(A, b, n_iter=100, regparam="gcv", x_true=None, **kwargs):
             if isinstance(regparam, str) and regparam == "gcv":
                 # svd(B) (:81) enters GCV through s and Q_A^T bhat = beta0 * (first row of the left vectors) only — and G(lam) is a
                 # resolvent of the tridiagonal B B^T: evaluated without the SVD (trk_host_gcv_bidiag); variant 'modified', fullsize = m (:84)
-                if kwargs.get("gcv_by_svd", False):
-                    s, u0 = bidiag_svd_first_row(gk._alphas[:k], gk._betas[:k])
-                    lam = fminbound_gcv_diag(s, gk.beta0 * u0, m)
-                else:
-                    lam = fminbound_gcv_bidiag(gk._alphas[:k], gk._betas[:k], gk.beta0, m)
+                lam = fminbound_gcv_bidiag(gk._alphas[:k], gk._betas[:k], gk.beta0, m)
             elif isinstance(regparam, str) and regparam == "l_curve":
                 bhat = np.zeros(k + 1)
                 bhat[0] = gk.beta0
@@ -358,12 +353,8 @@ def Hybrid_LSQR(A, b, n_iter=100, regparam="gcv", x_true=None, **kwargs):
                 # U^T b row by row, downloaded with each step's norms (krylov.GKState.step_prefetch): no pass over U, no blocking copy
                 bproj = np.asarray(gk.uproj[:k + 1]) / np.concatenate(([gk.beta0], gk._betas[:k]))   # rows of U are beta_j u_j
                 extra = {key: kwargs[key] for key in ("eta", "explicitProj") if key in kwargs}
-                if kwargs.get("dp_by_svd", False):
-                    s, proj = bidiag_svd_project(gk._alphas[:k], gk._betas[:k], bproj)       # svd(B_k), U^T bproj (dp :68-70)
-                    lam = discrepancy_principle(None, None, None, 0.0, delta=kwargs.get("delta"), L_is_identity=True,
-                                                spectrum=(s, proj, (k + 1, k)), **extra)
-                else:                                # the same Newton iteration on the tridiagonal resolvent: no SVD of B_k
-                    lam = discrepancy_principle_bidiag(gk._alphas[:k], gk._betas[:k], bproj, delta=kwargs.get("delta"), **extra)
+                # the Newton iteration of discrepancy_principle() (:68-70) on the tridiagonal resolvent: no SVD of B_k
+                lam = discrepancy_principle_bidiag(gk._alphas[:k], gk._betas[:k], bproj, delta=kwargs.get("delta"), **extra)
             else:
                 lam = regparam
             form_iterate(k, lam)

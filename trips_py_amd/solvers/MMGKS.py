@@ -16,7 +16,7 @@ from .. import _trace
 from .._io import Formatter, History, as_operator
 from ..engine import Coef
 from ..decompositions import golub_kahan_device
-from ..krylov import _plain_handle_apply, DeviceBasis, GramSchmidtByGram, orthogonalize
+from ..krylov import _plain_handle_apply, DeviceBasis, GramSchmidtByGram
 from ._common import check_delta, choose_lambda, gram_factor, gram_gcv_host, project_rhs, tikhonov_lstsq, small_host_blas
 
 
@@ -119,7 +119,7 @@ def MMGKS(A, b, L, pnorm=2, qnorm=1, projection_dim=3, n_iter=5, regparam="gcv",
     # (2048^2: 16 % of the device's time, and kmax x m floats of images)
     gcv_host = isinstance(regparam, str) and regparam == "gcv" and hasattr(eng, "gram_tikhonov") and kwargs.get("device_solve", True)
     unit_A = (pnorm == 2 and (on_dev or gcv_host) and dA and hasattr(eng, "gram_row_from_sweep") and hasattr(eng, "cgs_coeffs")
-              and kmax <= eng.GRAM_TIKHONOV_MAX_K and kwargs.get("gram_sweeps", True) and kwargs.get("unweighted_fidelity_gram", True))
+              and kmax <= eng.GRAM_TIKHONOV_MAX_K and kwargs.get("unweighted_fidelity_gram", True))
     AV = None if unit_A else DeviceBasis(eng, m, kmax)
     # the 2-D first-difference L has fused forms (trk_tv_weights / trk_tv_grad): L x is never written out
     fusedL = dL and getattr(L, "fused_tv", False) and not iso and not gs and kwargs.get("fused_tv", True)
@@ -149,7 +149,6 @@ def MMGKS(A, b, L, pnorm=2, qnorm=1, projection_dim=3, n_iter=5, regparam="gcv",
     A.apply(bv, out=x_cur, transpose=True)                                            # x = A^T b (:43)
     G = eng.scalars(2 * kmax * kmax + 2 * kmax + 2)
     Y = eng.scalars(kmax)
-    H = eng.scalars(2 * kmax)
     E = eng.scalars(n_iter + 3)
     Rn = eng.scalars(n_iter + 1)
     ax, tm, wf = eng.empty(m), eng.empty(m), eng.empty(m)
@@ -168,7 +167,7 @@ def MMGKS(A, b, L, pnorm=2, qnorm=1, projection_dim=3, n_iter=5, regparam="gcv",
         L.apply(x_cur, out=lx)
 
     # the two Gram-Schmidt sweeps per iteration by Gram matrix (two passes over V instead of three / four)
-    gs_gram = GramSchmidtByGram(eng, V, kmax) if (hasattr(eng, "cgs_coeffs") and kwargs.get("gram_sweeps", True)) else None
+    gs_gram = GramSchmidtByGram(eng, V, kmax)
     lams, res, lam, x_dev, its = [], [], None, None, 0
     xh_mm = None
     xh_buf = eng.zeros(2 * L.npix) if (fusedL and getattr(L, "sharded", False)) else None
@@ -176,8 +175,8 @@ def MMGKS(A, b, L, pnorm=2, qnorm=1, projection_dim=3, n_iter=5, regparam="gcv",
     if unit_wf:
         wf.fill_(1.0)
     # ||x_i - x_true||^2 rides the pass that forms x_i = V y (trk_gemv_n_err) as raw block partials
-    gram_ahead, fuse_passes = False, bool(kwargs.get("fuse_gram_passes", True))
-    err_fused = xt is not None and hasattr(eng, "gemv_n_err") and kwargs.get("fused_error_norm", True)
+    gram_ahead = False
+    err_fused = xt is not None and hasattr(eng, "gemv_n_err")
     EP_CAP = 2048
     EP, n_ep = (eng.scalars(EP_CAP * max(1, n_iter)) if err_fused else None), 0
     for ii in _trace.progress(range(n_iter), "running MMGKS...", kwargs.get("progress")):     # (MMGKS.py:55)
@@ -218,7 +217,7 @@ def MMGKS(A, b, L, pnorm=2, qnorm=1, projection_dim=3, n_iter=5, regparam="gcv",
             eng.allreduce(G, kk, 2 * kk)
             ga, _, cc = pbA.download_grams(k)
             gl = G.host(kk, 2 * kk).reshape(k, k)
-            one = gram_gcv_host(ga, gl, cc, cc) if kwargs.get("host_solve_in_c", True) else None
+            one = gram_gcv_host(ga, gl, cc, cc)
             if one is not None:
                 lam, y = one
             else:
@@ -247,7 +246,7 @@ def MMGKS(A, b, L, pnorm=2, qnorm=1, projection_dim=3, n_iter=5, regparam="gcv",
             eng.allreduce(G, 0, nred)
             g = G.host(0, nred)
             one = None
-            if isinstance(regparam, str) and regparam == "gcv" and kwargs.get("host_solve_in_c", True):
+            if isinstance(regparam, str) and regparam == "gcv":
                 # the whole projected problem in one library call (trk_host_gram_gcv): lambda from Q_A^T (wf*b), y from Q_A^T b (:97-106)
                 one = gram_gcv_host(g[:kk].reshape(k, k), g[kk:2 * kk].reshape(k, k), g[2 * kk + k:2 * kk + 2 * k], g[2 * kk:2 * kk + k])
             if one is not None:
@@ -278,7 +277,7 @@ def MMGKS(A, b, L, pnorm=2, qnorm=1, projection_dim=3, n_iter=5, regparam="gcv",
         last = ii == n_iter - 1
         _trace.mark("MMGKS: residual")
         # r = A^T (wf * (A x - b)) + lam L^T (wr * (L x))                              (:114-118)
-        fused_res = dA and unit_wf and hasattr(A, "apply_axpby") and _plain_handle_apply(A) and kwargs.get("fused_residual", True)
+        fused_res = dA and unit_wf and hasattr(A, "apply_axpby") and _plain_handle_apply(A)
         if fused_res:
             A.apply_axpby(x_dev, 1.0, -1.0, bv, tm)                                   # A x - b in the operator's own output pass
             res_a = None
@@ -318,26 +317,18 @@ def MMGKS(A, b, L, pnorm=2, qnorm=1, projection_dim=3, n_iter=5, regparam="gcv",
             eng.axpby(1.0, r, float(lam), rb, r)
         _trace.mark("MMGKS: orthogonalise, new basis vector, images")
         vn = V.next_slot()
-        # (GKS takes that row from the sweep's own pass over V; here r is NOT orthogonal to V — the residual carries the weights to
-        #  the first power, the projected problem to the second — so the coefficients c are not small and the row's algebra
-        #  amplifies fp32 rounding: the reference golden went from 2.4e-7 to 1.6e-5.  Opt-in only.)
-        merged = pbA is not None and gs_gram is not None and gs_gram.in_G == k - 1 and kwargs.get("gram_rows_from_sweep", False)
-        if merged:
-            cc = gs_gram.sweep(k, r, 2, vn, sumsq=Rn.ref(ii), extra=pbA.sweep_operands(r))   # ... and V^T (A^T A r) on the same pass
-        elif gs_gram is not None:
-            gs_gram.sweep(k, r, 2, vn, sumsq=Rn.ref(ii))                              # (:119-120) two sweeps, ||r||^2 fused
-        else:
-            orthogonalize(eng, V, k, r, H, 0, passes=2, out=vn, sumsq=Rn.ref(ii))
+        # (GKS takes the new vector's Gram row from the sweep's own pass over V; here r is NOT orthogonal to V — the residual carries
+        #  the weights to the first power, the projected problem to the second — so the coefficients c are not small and the row's
+        #  algebra amplifies fp32 rounding: the reference golden went from 2.4e-7 to 1.6e-5.  The row keeps a pass of its own.)
+        gs_gram.sweep(k, r, 2, vn, sumsq=Rn.ref(ii))                                  # (:119-120) two sweeps, ||r||^2 fused
         eng.allreduce(Rn, ii, ii + 1)
-        if pbA is not None and not merged:
+        if pbA is not None:
             pbA.normalise_new(Coef(1.0, den=Rn.ref(ii), sqrt_den=True), vn)          # vn = r / ||r|| (:121-123), with c_j = v_j . A^T b
         else:
             eng.scale(Coef(1.0, den=Rn.ref(ii), sqrt_den=True), vn, vn)              # vn = r / ||r|| (:121-123)
         V.commit()
-        if merged:
-            pbA.append_from_sweep(gs_gram, k, cc, Rn.ref(ii))
-        elif pbA is not None:
-            if tv_gram and fuse_passes and not last:
+        if pbA is not None:
+            if tv_gram and not last:
                 # the new Gram row V^T (A^T A v_new) and the NEXT iteration's re-weighted Gram of L V both sweep V (now k + 1 vectors):
                 # one pass (trk_wgram_tv_z).  The weights of the next iteration depend on x_dev only, which is final.
                 L.tv_weights(x_dev, epsilon, qnorm, wr, **({"halo": xh_mm} if xh_mm is not None else {}))
