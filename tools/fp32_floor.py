@@ -7,7 +7,7 @@ between the two runs is a floor for the parity bar of tests/test_gpu_configs_ful
 `c5cgls`: CGLS (no regularisation) on the C5 data: past semi-convergence (iterate ~25) the recurrence amplifies the roundings by four
 orders of magnitude — what tools/cgls_forms_accuracy.py measures for the engine's two arrangements on the GPU.
 `c3emul` (round 4): the ENGINE's own arrangement of Hybrid-LSQR at a fixed lambda restated in NumPy — Golub-Kahan on unnormalised
-vectors (trk_gk_step: include/trk.h), damped LSQR's short recurrence for the iterate (k_lsqr_damped_update: csrc/vecops.hip) — with
+vectors (trk_gk_step: include/trk.h), damped LSQR's short recurrence for the iterate (k_lsqr_damped_update: csrc/gemv.hip) — with
 float64 arithmetic everywhere and a rounding to float32 exactly where the engine STORES a vector (u, v, w, x; the operator's output
 once more, standing for the projector's own fp32 accumulation): what ANY fp32-storage run of that arrangement does, against the
 float64 oracle's iterates.  VERDICT r03 asked whether the engine's 1.6e-3 at iterate 7 is the arrangement's floor or a defect.

@@ -214,10 +214,8 @@ int trk_dot_pair(const float* q, const float* w, int64_t n, double* out3, trk_st
   const int grid = grid_for(n);
   double* part = nullptr;
   if (int rc = scratch_doubles(s, (size_t)grid * 3, &part)) return rc;
-  if (aligned16(q) && (!w || aligned16(w)))
-    hipLaunchKernelGGL((k_dot_pair<true>), dim3(grid), dim3(NT), 0, s, q, w, n, part);
-  else
-    hipLaunchKernelGGL((k_dot_pair<false>), dim3(grid), dim3(NT), 0, s, q, w, n, part);
+  with_bools([&](auto VEC) { hipLaunchKernelGGL((k_dot_pair<VEC>), dim3(grid), dim3(NT), 0, s, q, w, n, part); },
+             aligned16(q) && (!w || aligned16(w)));
   TRK_LAUNCH_CHECK();
   return finalize_sums(part, grid, 3, 3, out3, s);
 }
@@ -226,21 +224,17 @@ int trk_cgls_sharded_scalars(const float* q, const float* w, int64_t m, const do
                              trk_stream st) {
   TRK_REQUIRE(q && G4 && m >= 0 && n_gamma >= 0 && (n_gamma == 0 || gamma_partials), "trk_cgls_sharded_scalars: bad argument");
   hipStream_t s = (hipStream_t)st;
+  const bool vec = aligned16(q) && (!w || aligned16(w));
   if (m <= kOneBlockMax && n_gamma <= (1 << 16)) {
-    if (aligned16(q) && (!w || aligned16(w)))
-      hipLaunchKernelGGL((k_sharded_scalars<true>), dim3(1), dim3(NT1), 0, s, q, w, m, gamma_partials, n_gamma, G4);
-    else
-      hipLaunchKernelGGL((k_sharded_scalars<false>), dim3(1), dim3(NT1), 0, s, q, w, m, gamma_partials, n_gamma, G4);
+    with_bools([&](auto VEC) { hipLaunchKernelGGL((k_sharded_scalars<VEC>), dim3(1), dim3(NT1), 0, s, q, w, m, gamma_partials, n_gamma, G4); },
+               vec);
     TRK_LAUNCH_CHECK();
     return TRK_OK;
   }
   const int grid = grid_for(m);
   double* part = nullptr;
   if (int rc = scratch_doubles(s, (size_t)grid * 3, &part)) return rc;
-  if (aligned16(q) && (!w || aligned16(w)))
-    hipLaunchKernelGGL((k_dot_pair<true>), dim3(grid), dim3(NT), 0, s, q, w, m, part);
-  else
-    hipLaunchKernelGGL((k_dot_pair<false>), dim3(grid), dim3(NT), 0, s, q, w, m, part);
+  with_bools([&](auto VEC) { hipLaunchKernelGGL((k_dot_pair<VEC>), dim3(grid), dim3(NT), 0, s, q, w, m, part); }, vec);
   hipLaunchKernelGGL(k_sharded_finalize, dim3(4), dim3(256), 0, s, part, grid, gamma_partials, n_gamma, G4);
   TRK_LAUNCH_CHECK();
   return TRK_OK;
@@ -260,12 +254,10 @@ int trk_cgls_sharded_update(int64_t n, int64_t m, const double* G4, const double
   *n_blocks = grid;
   const bool vec = aligned16(x) && aligned16(p) && aligned16(t) && aligned16(x_new) && aligned16(r) && aligned16(q) &&
                    aligned16(w) && (!x_true || aligned16(x_true));
-#define SU(XT, VC)                                                                                                      \
-  hipLaunchKernelGGL((k_cgls_sharded_update<XT, VC>), dim3(grid), dim3(NT), 0, s, n, m, G4, gamma_prev, first, x, \
-                     p, t, x_new, r, q, w, x_true, publish_delta, publish_gamma, norm_partials)
-  if (x_true) { if (vec) SU(true, true); else SU(true, false); }
-  else        { if (vec) SU(false, true); else SU(false, false); }
-#undef SU
+  with_bools([&](auto HAS_XT, auto VEC) {
+    hipLaunchKernelGGL((k_cgls_sharded_update<HAS_XT, VEC>), dim3(grid), dim3(NT), 0, s, n, m, G4, gamma_prev, first, x, p, t, x_new, r, q, w,
+                       x_true, publish_delta, publish_gamma, norm_partials);
+  }, x_true != nullptr, vec);
   TRK_LAUNCH_CHECK();
   return TRK_OK;
 }

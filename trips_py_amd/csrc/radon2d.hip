@@ -2090,7 +2090,7 @@ __global__ __launch_bounds__(256 * G) void k_radon_adj_tile(const float* __restr
   }
   if (epi.lq.on) {                                                // uniform over the grid
     // the damped-LSQR step of the iterate that z = V[k-1] belongs to, on this workgroup's pixels: k_lsqr_damped_update's
-    // arithmetic, expression for expression (vecops.hip) — the same floats whichever kernel forms them
+    // arithmetic, expression for expression (gemv.hip) — the same floats whichever kernel forms them
     const LsqrReq& L = epi.lq;
     __shared__ double lcf[3];
     __syncthreads();

@@ -9,7 +9,7 @@
 //     One thread per ray (forward) / per pixel (adjoint, gather over the rays that touch it: matched to the forward tap by tap).
 //   * the vector kernels of a Golub-Kahan half step on the element type: out = a Op(x) + b z (float64 coefficients and
 //     products, ONE rounding to T — the arithmetic of the production projector's epilogue, radon2d.hip epi_combine) with the fused
-//     sum of squares; the damped-LSQR update is the production template itself (vecops.hip, k_lsqr_damped_update<T, ..>).
+//     sum of squares; the damped-LSQR update is the production template itself (gemv.hip, k_lsqr_damped_update<T, ..>).
 //   * trk_gk_lsqr_chain: the engine's arrangement of Hybrid-LSQR at a fixed lambda (krylov.GKState(normalized=False): U[j] =
 //     beta_j u_j, V[j] = alpha_j v_j, squared norms as device doubles, the divisions folded into the next step's coefficients;
 //     x_k by Paige & Saunders' short recurrence) on vectors of type T, enqueued by one call.

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <type_traits>
 #include "trk.h"
 
 namespace trk {
@@ -316,6 +317,18 @@ inline int stream_nontemporal(int64_t n) {
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// Run-time booleans to compile-time ones for a launcher: f is a generic lambda that receives one std::true_type / std::false_type per
+// boolean and uses them as template arguments — ONE launch expression stands for the full product of its kernel's bool parameters:
+//   with_bools([&](auto HAS_Y, auto VEC) { hipLaunchKernelGGL((k<HAS_Y, VEC>), ...); }, y != nullptr, vec);
+// A launcher that instantiates only some combinations keeps its own ladder.
+template <class F>
+inline void with_bools(F&& f) { f(); }
+template <class F, class... Rest>
+inline void with_bools(F&& f, bool b, Rest... rest) {
+  if (b) with_bools([&](auto... c) { f(std::true_type{}, c...); }, rest...);
+  else with_bools([&](auto... c) { f(std::false_type{}, c...); }, rest...);
+}
+
 }  // namespace trk
 
 // ------------------------------------------------------------------ kernel timer (hipEvent pairs)
@@ -367,11 +380,11 @@ struct RadonRefGeom {
 bool radon_ref_geometry(trk_op* op, RadonRefGeom* g);
 int radon_ref_apply_f32(const RadonRefGeom& g, int transpose, int weights, const float* x, float* y, hipStream_t s);
 int ref_axpby_f32(int64_t n, Coef a, const float* x, Coef b, const float* z, float* out, double* sumsq, hipStream_t s);
-// vecops.hip: k_lsqr_damped_update<T, ..> for T = float (elem_bytes 4) / double (8), no error partials
+// gemv.hip: k_lsqr_damped_update<T, ..> for T = float (elem_bytes 4) / double (8), no error partials
 int lsqr_damped_update_any(size_t elem_bytes, const void* vk, void* w, const void* x_in, void* x_out, int64_t n, const double* alpha_sq,
                            const double* beta_next_sq, const double* beta0_sq, double damp, const double* state_in, double* state_out,
                            int first, hipStream_t s);
-// vecops.hip: trk_gemv_t2 / trk_gemv_n without their finalize launch (the block partials stay in the stream's scratch: *part, *nblk),
+// gemv.hip: trk_gemv_t2 / trk_gemv_n without their finalize launch (the block partials stay in the stream's scratch: *part, *nblk),
 // and the normalisation x / sqrt(sum of partials) that adds them up itself (k_finalize's order) and leaves the sum in *sum_out;
 // post.on: workgroup 0 also carries a mailbox post (as the Golub-Kahan adjoint half step does)
 int gemv_t2_partials(const float* V, int64_t ld, int k, int64_t n, const float* r, const float* r2, double** part, int* nblk, hipStream_t s);
