@@ -379,6 +379,22 @@ int trk_cgls_r_update(int64_t m, const double* gamma_old, const double* delta, i
 int trk_cgls_xp_update(int64_t n, const double* gamma_old, const double* delta, const double* gamma_new, int gamma_new_n,
                        const float* x, float* p, const float* t, float* x_new, const float* x_true, double* publish_gamma,
                        double* norm_partials, int capacity_blocks, int* n_blocks, trk_stream stream);
+/* Without a history x feeds nothing but the next x, so its update can wait: the directions of `count` iterations are kept and ONE pass
+ * makes their x updates (count - 1 writes of x are not made; same fp32 operations in the same order, same bits).
+ *   trk_cgls_p_update_to: trk_cgls_p_update with a destination, p_out = t + (S(gamma_new) / *gamma_old) p (p_out may be p).
+ *   trk_cgls_xs_update: iterations k_last - count + 1 .. k_last, 1 <= count <= 8.  Their directions sit in s_slots >= count slots used
+ *   round-robin — slot 0 is p, slot j is ring + (j - 1) * ring_ld (ring may be NULL for s_slots = 1) — starting at slot `first`.
+ *   x = x_{k_last - count}; x_new = x_{k_last} (may be x); every intermediate iterate is formed in registers and its three norms go
+ *   to its own slice NP + 3 * *n_blocks * (j - 1), as trk_cgls_xp_update leaves them.  Step j is S[5(j-1)+1] / S[5j] (gamma_{j-1} /
+ *   delta_j; S[0] for j = 1), finished scalars of the layout of trk_cgls_iterate.  p_out = t + (S(gamma_new) / gamma_{k_last - 1})
+ *   p_{k_last} (may be any of the slots; fastest for what reads it next when it is p_{k_last}'s own); block 0 stores the finished
+ *   gamma_new to S[5 k_last + 1].  All vectors 16-byte aligned.  Inputs that are not read again soon are loaded non-temporally (also
+ *   by trk_cgls_p_update_to when p_out is not p). */
+int trk_cgls_p_update_to(int64_t n, const float* t, const float* p, float* p_out, const double* gamma_new, int gamma_new_n,
+                         const double* gamma_old, double* publish_gamma, trk_stream stream);
+int trk_cgls_xs_update(int64_t n, int count, int k_last, double* S, const double* gamma_new, int gamma_new_n, const float* x,
+                       const float* p, const float* ring, int64_t ring_ld, int s_slots, int first, const float* t, float* x_new,
+                       float* p_out, const float* x_true, double* NP, int capacity_blocks, int* n_blocks, trk_stream stream);
 
 /* ---------------------------------------------------------------- fused CGLS fast path --- */
 /* For operators whose kernel can combine two inputs on load (the blur): one CGLS iteration becomes three launches with no
@@ -516,6 +532,18 @@ int trk_cgls_iterate(trk_op* A, int k_first, int n_iters, float* p, float* r, fl
                      int keep_history, const float* x_prev, const float* x_true, double* S, double* NP,
                      int np_capacity_blocks, int* n_np_inout, double* PG, double* PD, int pcap, int grouping,
                      trk_stream stream);
+/* trk_cgls_iterate for keep_history = 0, raw partials (PG, PD required, operator with a fused apply) and grouping 1, with the x updates
+ * made s at a time: forward apply from the current direction, trk_cgls_r_update, adjoint apply, then trk_cgls_p_update_to into the next
+ * of s slots (p and the ring, round-robin) or — every s-th iteration and on the last one of the call — trk_cgls_xs_update over the
+ * pending directions, the new direction written over the current one (into p at the end of the call).  ring: s - 1
+ * vectors of row stride ring_ld (scratch: nothing in it outlives the call; NULL for s = 1), s <= 8.  On return everything is where
+ * trk_cgls_iterate would have left it, bit for bit: x_{k_last} in X[(k_last - 1) & 1], the current direction in p, r, t, w, S, NP,
+ * *n_np_inout — a later call of either function, or single launches, continue from it.
+ * trk_cgls_x_batch: the s to use for vectors of n floats (1 = off; measured rule). */
+int trk_cgls_x_batch(int64_t n);
+int trk_cgls_iterate_xbatch(trk_op* A, int k_first, int n_iters, float* p, float* ring, int64_t ring_ld, int s, float* r, float* t,
+                            float* w, float* X, int64_t x_ld, const float* x_prev, const float* x_true, double* S, double* NP,
+                            int np_capacity_blocks, int* n_np_inout, double* PG, double* PD, int pcap, trk_stream stream);
 /* The same for operators with a fused apply (trk_op_fused_caps): three launches per iteration.  P, R: ping-pong pairs
  * [2][p_ld], [2][r_ld] (iteration k reads index (k-1) & 1, writes k & 1); PG / PD: gamma / delta block partials with
  * `pcap` doubles each; *n_g_inout: number of valid gamma partials in PG (set by the caller's r0/t0 setup). */

@@ -223,6 +223,13 @@ SIGNATURES = {
     "trk_cgls_xp_update": (c_int, [c_i64, c_f64p, c_f64p, c_f64p, c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f64p, c_f64p,
                                    c_int, ctypes.POINTER(c_int), c_stream]),
     "trk_cgls_p_update": (c_int, [c_i64, c_f32p, c_f32p, c_f64p, c_int, c_f64p, c_f64p, c_stream]),
+    "trk_cgls_p_update_to": (c_int, [c_i64, c_f32p, c_f32p, c_f32p, c_f64p, c_int, c_f64p, c_f64p, c_stream]),
+    "trk_cgls_xs_update": (c_int, [c_i64, c_int, c_int, c_f64p, c_f64p, c_int, c_f32p, c_f32p, c_f32p, c_i64, c_int, c_int, c_f32p,
+                                   c_f32p, c_f32p, c_f32p, c_f64p, c_int, ctypes.POINTER(c_int), c_stream]),
+    "trk_cgls_x_batch": (c_int, [c_i64]),
+    "trk_cgls_iterate_xbatch": (c_int, [c_op, c_int, c_int, c_f32p, c_f32p, c_i64, c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_i64,
+                                        c_f32p, c_f32p, c_f64p, c_f64p, c_int, ctypes.POINTER(c_int), c_f64p, c_f64p, c_int,
+                                        c_stream]),
     "trk_cgls_iterate_fused": (c_int, [c_op, c_int, c_int, c_f32p, c_i64, c_f32p, c_i64, c_f32p, c_f32p, c_f32p, c_i64, c_int,
                                        c_f32p, c_f32p, c_f64p, c_f64p, c_f64p, c_int, c_f64p, c_int, ctypes.POINTER(c_int),
                                        ctypes.POINTER(c_int), c_stream]),

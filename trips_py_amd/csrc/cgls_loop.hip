@@ -84,6 +84,66 @@ int trk_cgls_iterate(trk_op* A, int k_first, int n_iters, float* p, float* r, fl
   return TRK_OK;
 }
 
+// How many x updates the history-less raw-partials iteration (grouping 1) defers and then makes in ONE pass (trk_cgls_iterate_xbatch);
+// 1 = off.  Measured (iterations/s, s = 1 / 2 / 4 / 8, median of three):
+//   3072^2 12.0 k / 12.3 k / 12.6 k / 12.6 k | 3584^2 9.32 k / 9.57 k / 9.73 k / 9.81 k | 4096^2 7.64 k / 7.87 k / 8.06 k / 8.09 k |
+//   4608^2 6.12 k / 6.26 k / 6.34 k / 6.44 k | 5120^2 5.09 k / 5.28 k / 5.32 k / 5.31 k | 6144^2 3.17 k / 3.18 k / 3.19 k / 3.17 k |
+//   8192^2 1.75 k / 1.77 k / 1.77 k / 1.79 k
+// (profiles/xbatch/sweep.txt).
+// s = 8 is the fastest or level at every size the regrouped updates are used at, so the threshold is theirs (trk_cgls_update_grouping);
+// the ten-stream k_cgls_xs_update<8> streams a little below <4> (805 MB in 140 us = 5.8 TB/s against 537 MB in 88 us = 6.1 TB/s at
+// 4096^2) and still pays for the writes it saves.
+int trk_cgls_x_batch(int64_t n) {
+  return n >= ((int64_t)8 << 20) ? 8 : 1;
+}
+
+int trk_cgls_iterate_xbatch(trk_op* A, int k_first, int n_iters, float* p, float* ring, int64_t ring_ld, int s, float* r, float* t,
+                            float* w, float* X, int64_t x_ld, const float* x_prev, const float* x_true, double* S, double* NP,
+                            int np_capacity_blocks, int* n_np_inout, double* PG, double* PD, int pcap, trk_stream stream) {
+  TRK_REQUIRE(A && p && r && t && w && X && x_prev && S && NP && n_np_inout && PG && PD && pcap > 0,
+              "trk_cgls_iterate_xbatch: NULL argument");
+  TRK_REQUIRE(A->apply_fused, "trk_cgls_iterate_xbatch: the operator has no fused apply (trk_op_fused_caps)");
+  TRK_REQUIRE(k_first >= 1 && n_iters >= 0, "trk_cgls_iterate_xbatch: need k_first >= 1, n_iters >= 0");
+  TRK_REQUIRE(s >= 1 && (s == 1 || (ring && ring_ld >= A->cols)), "trk_cgls_iterate_xbatch: s > 1 needs a ring of s - 1 directions");
+  const int64_t m = A->rows, n = A->cols;
+  int n_np = *n_np_inout;
+  // the directions live in s slots (0: the caller's p, j: ring row j - 1) used round-robin; `cur` holds p_k, the `pending` slots up to
+  // it the directions of the iterations whose x update is still to be made
+  auto slot = [&](int j) { return j == 0 ? p : ring + (int64_t)(j - 1) * ring_ld; };
+  int cur = 0, pending = 0;
+  const int k_end = k_first + n_iters;
+  for (int k = k_first; k < k_end; ++k) {
+    double* row = S + 5 * (int64_t)k;                     // [delta, gamma, ||x||^2, ||dx||^2, ||x-xt||^2]
+    const double* gamma_old = (k == 1) ? S : row - 4;
+    float* p_k = slot(cur);
+    int n_d = 0, n_g = 0;
+    int rc = trk_op_apply_fused(A, 0, p_k, nullptr, 0.0, nullptr, 0, nullptr, 0, nullptr, w, PD, pcap, &n_d, stream);
+    if (rc) return rc;
+    rc = trk_cgls_r_update(m, gamma_old, PD, n_d, r, w, row, stream);
+    if (rc) return rc;
+    rc = trk_op_apply_fused(A, 1, r, nullptr, 0.0, nullptr, 0, nullptr, 0, nullptr, t, PG, pcap, &n_g, stream);
+    if (rc) return rc;
+    const bool last = k + 1 == k_end;
+    if (++pending < s && !last) {                         // p_{k+1} into the next slot; x waits
+      cur = (cur + 1) % s;
+      rc = trk_cgls_p_update_to(n, t, p_k, slot(cur), PG, n_g, gamma_old, row + 1, stream);
+      if (rc) return rc;
+      continue;
+    }
+    // x_{k-pending+1} .. x_k in one pass, x_k written to the slot trk_cgls_iterate writes it to; p_{k+1} over p_k (in place: it stays
+    // cached for the next forward apply), at the end of the call into the caller's p
+    float* x_new = X + (int64_t)((k - 1) & 1) * x_ld;
+    rc = trk_cgls_xs_update(n, pending, k, S, PG, n_g, x_prev, p, ring, ring_ld, s, (cur - pending + 1 + s) % s, t, x_new,
+                            last ? p : p_k, x_true, NP, np_capacity_blocks, &n_np, stream);
+    if (rc) return rc;
+    x_prev = x_new;
+    pending = 0;
+    if (last) cur = 0;
+  }
+  *n_np_inout = n_np;
+  return TRK_OK;
+}
+
 int trk_cgls_iterate_fused(trk_op* A, int k_first, int n_iters, float* P, int64_t p_ld, float* R, int64_t r_ld, float* t,
                            float* w, float* X, int64_t x_ld, int keep_history, const float* x_prev, const float* x_true,
                            double* S, double* PG, double* PD, int pcap, double* NP, int np_capacity_blocks,

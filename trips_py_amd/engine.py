@@ -549,6 +549,22 @@ class HipEngine:
         _lib.check(rc, "trk_cgls_iterate")
         return c.value
 
+    def cgls_x_batch(self, n):
+        """How many x updates the history-less raw-partials CGLS iteration makes in one pass for vectors of n floats (1: off)."""
+        return int(self.lib.trk_cgls_x_batch(int(n)))
+
+    def cgls_iterate_xbatch(self, handle, k_first, n_iters, p, ring, s, r, t, w, X, x_prev, x_true, S, NP, np_cap, n_np, PG, PD, pcap):
+        """cgls_iterate without a history, raw partials, grouping 1, the x updates made s at a time (ring: [s - 1, n] scratch
+        directions, None for s = 1); returns the partial-block count."""
+        c = ctypes.c_int(int(n_np))
+        rc = self.lib.trk_cgls_iterate_xbatch(handle, int(k_first), int(n_iters), p.data_ptr(),
+                                              None if ring is None else ring.data_ptr(), 0 if ring is None else ring.stride(0),
+                                              int(s), r.data_ptr(), t.data_ptr(), w.data_ptr(), X.data_ptr(), X.stride(0),
+                                              x_prev.data_ptr(), None if x_true is None else x_true.data_ptr(), _ptr(S), _ptr(NP),
+                                              int(np_cap), ctypes.byref(c), _ptr(PG), _ptr(PD), int(pcap), self.stream())
+        _lib.check(rc, "trk_cgls_iterate_xbatch")
+        return c.value
+
     def cgls_iterate_fused(self, handle, k_first, n_iters, P, R, t, w, X, keep, x_prev, x_true, S, PG, PD, pcap, NP, np_cap,
                            n_g, n_np):
         """n_iters fused (3-launch) CGLS iterations in one library call; returns (n_g, n_np)."""
