@@ -414,8 +414,10 @@ def test_sparse_operator_and_reference_built_regularisers():
 @pytest.mark.parametrize("shape,density", [((1000, 3000), 0.001), ((512, 512), 0.012), ((300, 4000), 0.05), ((64, 9000), 0.3), ((7, 5), 0.5),
                                            ((2000, 50), 0.02)])
 def test_csr_group_kernel_every_group_size(shape, density):
-    """k_csr_group<G> for every lanes-per-row choice (mean row lengths 3 .. 2700: G = 4 .. 64; and empty rows, rows longer than
-    2 G, a matrix with fewer rows than a wave has groups), both directions, against scipy on the fp32-rounded operands."""
+    """k_csr_group<G> on scipy.sparse.random matrices whose mean row lengths (1 .. 2700 over the two directions) give every
+    lanes-per-row choice G = 2 .. 16, one of them with fewer rows than a wave has groups; both directions, against scipy on the
+    fp32-rounded operands, by the norm of the whole vector.  The row lengths cluster at the mean: empty rows and rows many times
+    longer than 4 G occur only by chance here.  Every row-length path of the kernel, entry by entry: tests/test_gpu_spmv_accuracy.py."""
     import scipy.sparse as sp
     from trips_py_amd.operators import SparseOp
     M = sp.random(shape[0], shape[1], density=density, random_state=shape[0] + shape[1], format="csr")
