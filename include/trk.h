@@ -832,12 +832,24 @@ int trk_cgls_iterate_sharded(trk_op* A, trk_comm* comm, int k_first, int n_iters
  *   (at most max_sweeps; the last one is the sweep that found every pair orthogonal), *converged = 1 when that sweep happened.
  *   Bitwise reproducible (fixed summation orders, no atomics).  Two host synchronisations per sweep (the column order by norm, the
  *   sweep's verdict).
+ * trk_dense_svd_carry_f64 (and its _dims): the same iteration, but the matrix rotated alongside G is the caller's companion C
+ *   (nc >= 1 rows, ldc >= nc, npad columns) instead of the identity: its first n columns are read as given, columns n..npad are
+ *   zeroed by the call, and C times the accumulated rotation comes back.  The rotations depend on A alone, so G, S, *sweeps and
+ *   every row of the result are those trk_dense_svd_f64 gives for the same A (a row e_i^T of C comes back as row i of V, bit
+ *   for bit).  Workspace and npad as for trk_dense_svd_f64.
+ * trk_dense_colnorm_f64: out[j] = ||X[0..rows, j]|| for `cols` columns of a column-major X (ldx >= rows), the fixed-order sum
+ *   that gives S.
  * trk_dense_gemv_f64: y = beta y + alpha op(A) (d .* x), op(A) = A^T (trans = 1: y has n entries, x and d m) or A (trans = 0: y has
  *   m entries, x and d n); d may be NULL (all ones); beta = 0 does not read y.  Fixed summation order. */
 #define TRK_DENSE_SVD_MAX_COLS 8192
 int trk_dense_svd_f64_dims(int64_t m, int64_t n, int64_t* npad, int64_t* work_doubles);
 int trk_dense_svd_f64(const double* A, int64_t m, int64_t n, int64_t lda, double* G, int64_t ldg, double* V, int64_t ldv, double* S,
                       double* work, int64_t work_doubles, double tol, int max_sweeps, int* sweeps, int* converged, trk_stream stream);
+int trk_dense_svd_carry_f64_dims(int64_t m, int64_t n, int64_t nc, int64_t* npad, int64_t* work_doubles);
+int trk_dense_svd_carry_f64(const double* A, int64_t m, int64_t n, int64_t lda, double* G, int64_t ldg, double* C, int64_t nc,
+                            int64_t ldc, double* S, double* work, int64_t work_doubles, double tol, int max_sweeps, int* sweeps,
+                            int* converged, trk_stream stream);
+int trk_dense_colnorm_f64(const double* X, int64_t ldx, int64_t rows, int64_t cols, double* out, trk_stream stream);
 int trk_dense_gemv_f64(int trans, int64_t m, int64_t n, const double* A, int64_t lda, const double* x, const double* d, double alpha,
                        double beta, double* y, trk_stream stream);
 

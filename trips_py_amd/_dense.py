@@ -1,5 +1,6 @@
-"""Dense float64 matrices on the device for the direct solvers (tSVD, Tikhonov): operand conversion, the one-sided Jacobi
-SVD of csrc/dense_svd.hip (trk_dense_svd_f64) and its two float64 products (trk_dense_gemv_f64).
+"""Dense float64 matrices on the device for the direct solvers (tSVD, tGSVD, Tikhonov): operand conversion, the one-sided Jacobi
+SVD of csrc/dense_svd.hip (trk_dense_svd_f64), the same iteration with a carried companion (trk_dense_svd_carry_f64) and the GSVD
+built on it, and the two float64 products (trk_dense_gemv_f64).
 
 A device matrix is held as a torch float64 tensor `At` of shape (n, m), contiguous: row j of `At` is column j of the m x n matrix,
 i.e. the column-major layout the kernels read (leading dimension m)."""
@@ -95,6 +96,135 @@ def svd_device_t(At, m, n, max_sweeps=MAX_SWEEPS):
         return _svd_tall(At, m, n, max_sweeps)
     Ut, S, Vt, sw = _svd_tall(At.T.contiguous(), n, m, max_sweeps)   # A^T = U' S V'^T  ->  A = V' S U'^T
     return Vt, S, Ut, sw
+
+
+def svd_carry_t(At, m, n, Ct, max_sweeps=MAX_SWEEPS):
+    """One-sided Jacobi on the m x n (m >= n) column-major At with a carried companion (trk_dense_svd_carry_f64): Ct is (n, nc),
+    row j the companion's column j.  With W the accumulated rotation, returns (Gt (n, m) = (A W)^T, S (n,) = its column norms,
+    (C W)^T (n, nc), sweeps) — in the order of A's columns, neither sorted nor normalised."""
+    eng = _engine()
+    lib = eng.lib
+    nc = int(Ct.shape[1])
+    if tuple(At.shape) != (n, m) or int(Ct.shape[0]) != n:
+        raise ValueError(f"svd_carry_t: At {tuple(At.shape)} and Ct {tuple(Ct.shape)} do not fit an {m} x {n} matrix")
+    npad, need = ctypes.c_int64(0), ctypes.c_int64(0)
+    _lib.check(lib.trk_dense_svd_carry_f64_dims(m, n, nc, ctypes.byref(npad), ctypes.byref(need)), "trk_dense_svd_carry_f64_dims")
+    npad = npad.value
+    At = At.contiguous()
+    G = torch.empty((npad, m), dtype=torch.float64, device=eng.device)
+    C = torch.empty((npad, nc), dtype=torch.float64, device=eng.device)
+    C[:n].copy_(Ct)
+    S = torch.empty(n, dtype=torch.float64, device=eng.device)
+    work = torch.empty(need.value, dtype=torch.float64, device=eng.device)
+    sweeps, conv = ctypes.c_int(0), ctypes.c_int(0)
+    tol = max(m, 64) * np.finfo(np.float64).eps
+    _lib.check(lib.trk_dense_svd_carry_f64(At.data_ptr(), m, n, m, G.data_ptr(), m, C.data_ptr(), nc, nc, S.data_ptr(),
+                                           work.data_ptr(), need.value, float(tol), int(max_sweeps), ctypes.byref(sweeps),
+                                           ctypes.byref(conv), eng.stream()), "trk_dense_svd_carry_f64")
+    if not conv.value:
+        warnings.warn(f"dense SVD: {m} x {n} not converged after {sweeps.value} Jacobi sweeps", RuntimeWarning)
+    return G[:n], S, C[:n], sweeps.value
+
+
+def colnorm(Xt, row0, rows):
+    """Norms of the columns of rows [row0, row0 + rows) of the column-major matrix Xt (cols, ld): the fixed-order sum of the SVD's
+    own singular values (trk_dense_colnorm_f64), where a torch reduction would not promise the same bits twice."""
+    eng = _engine()
+    cols, ld = int(Xt.shape[0]), int(Xt.shape[1])
+    if not Xt.is_contiguous() or row0 < 0 or rows < 1 or row0 + rows > ld:
+        raise ValueError(f"colnorm: rows [{row0}, {row0 + rows}) of a contiguous ({cols}, {ld}) tensor")
+    out = torch.empty(cols, dtype=torch.float64, device=eng.device)
+    _lib.check(eng.lib.trk_dense_colnorm_f64(Xt.data_ptr() + 8 * row0, ld, rows, cols, out.data_ptr(), eng.stream()),
+               "trk_dense_colnorm_f64")
+    return out
+
+
+def gsvd_shapes(A, L):
+    """(m, p, n) of the pair A (m x n), L (p x n), from the operands' `.shape` alone (nothing touches the engine): ValueError
+    unless both are 2-D with the same column count, m >= n, p >= n and n <= MAX_COLS."""
+    shapes = []
+    for X, role in ((A, "A"), (L, "L")):
+        shp = tuple(int(v) for v in (X.shape if hasattr(X, "shape") else np.shape(X)))
+        if len(shp) != 2:
+            raise ValueError(f"gsvd: {role} must be a 2-D matrix, got shape {shp}")
+        shapes.append(shp)
+    (m, n), (p, n2) = shapes
+    if n != n2:
+        raise ValueError(f"gsvd: A is {m} x {n} and L is {p} x {n2}: the column counts differ")
+    if n < 1 or m < n or p < n:
+        raise ValueError(f"gsvd: need m >= n, p >= n and n >= 1 for A m x n and L p x n (A is {m} x {n}, L is {p} x {n})")
+    if n > MAX_COLS:
+        raise ValueError(f"gsvd: at most {MAX_COLS} columns; got {n}")
+    return m, p, n
+
+
+class GSVD:
+    """The factors of gsvd_device as float64 device tensors, every matrix column-major (row i = column i):
+        Gt (n, m) = (U diag(c))^T,  Ht (n, p) = (V diag(s))^T,  Xt (n, n) = X^T,  Yt (n, n) = (X^-T)^T,  c ascending, s,
+    so that A = G X^T, L = H X^T and Y^T X = I; sweeps = Jacobi sweeps of the stages (0 for a stage that did not run)."""
+
+    def __init__(self, m, p, n, Gt, Ht, Xt, Yt, c, s, sweeps):
+        self.m, self.p, self.n = m, p, n
+        self.Gt, self.Ht, self.Xt, self.Yt, self.c, self.s, self.sweeps = Gt, Ht, Xt, Yt, c, s, sweeps
+
+    def _inv(self, d):
+        ok = d > self.n * np.finfo(np.float64).eps
+        return torch.where(ok, 1.0 / torch.where(ok, d, torch.ones_like(d)), torch.zeros_like(d))
+
+    def inv_c(self):
+        """1 / c, and 0 where c <= n eps (the columns of U that are zero by convention)."""
+        return self._inv(self.c)
+
+    def Ut(self):
+        return self.Gt * self.inv_c().reshape(-1, 1)
+
+    def Vt(self):
+        return self.Ht * self._inv(self.s).reshape(-1, 1)
+
+
+def gsvd_device(A, L, max_sweeps=MAX_SWEEPS):
+    """GSVD of the pair (A m x n, L p x n; m >= n, p >= n, [A; L] of full column rank) on the device -> GSVD.
+    Three runs of the one-sided Jacobi (docs/kernels/dense_svd.md, "GSVD"):
+      1. M = [A; L] = Q diag(sigma) Vm^T; ValueError when sigma_min <= max(m + p, n) eps sigma_max (A and L share a null space).
+      2. Q1 = Q[:m] with the companion [Q2; Vm diag(sigma); Vm diag(1 / sigma)]: G = Q1 W, Q2 W, X = Vm diag(sigma) W and
+         Y = X^-T come back together; c, s = column norms of G and Q2 W.
+      3. on the columns J with c > 1 / sqrt(2), where Q2 W has small and poorly orthogonal columns: Q2 W_J with the companion
+         [G_J; X_J; Y_J]; c and s on J again from the column norms.  Skipped when J is empty.
+    Then the columns are sorted by c ascending (s descending), the reference's order.
+    An s that should be zero (L has a null vector) comes out of the rotations as rounding of its O(1) neighbours, of order
+    sqrt(n) tol, not n eps.  What lies within 8 (m + p) eps cond(M) of zero — the accuracy of every s here — is returned as
+    exactly 0, with a zero column in H."""
+    m, p, n = gsvd_shapes(A, L)
+    At, _, _ = to_device_t(A, "A")
+    Lt, _, _ = to_device_t(L, "L")
+    eps = np.finfo(np.float64).eps
+    Qt, sig, Vmt, sw1 = _svd_tall(torch.cat((At, Lt), dim=1), m + p, n, max_sweeps)
+    smax, smin = float(sig[0]), float(sig[-1])
+    if not smin > max(m + p, n) * eps * smax:
+        raise ValueError(f"gsvd: [A; L] has no full column rank to working precision (sigma_min = {smin:.3e}, sigma_max = "
+                         f"{smax:.3e}): A and L share a null space")
+    sc = sig.reshape(-1, 1)
+    Gt, c, Ct, sw2 = svd_carry_t(Qt[:, :m].contiguous(), m, n, torch.cat((Qt[:, m:], Vmt * sc, Vmt / sc), dim=1), max_sweeps)
+    Ht, XYt = Ct[:, :p].contiguous(), Ct[:, p:]
+    s = colnorm(Ht, 0, p)
+    J = torch.nonzero(c > np.sqrt(0.5)).reshape(-1)
+    sw3 = 0
+    if J.numel() > 0:
+        nJ = int(J.numel())
+        comp = torch.cat((Gt.index_select(0, J), XYt.index_select(0, J)), dim=1)
+        HJ, sJ, comp, sw3 = svd_carry_t(Ht.index_select(0, J), p, nJ, comp, max_sweeps)
+        comp = comp.contiguous()
+        Gt, XYt = Gt.clone(), XYt.clone()
+        Gt.index_copy_(0, J, comp[:, :m])
+        XYt.index_copy_(0, J, comp[:, m:])
+        Ht.index_copy_(0, J, HJ)
+        c = c.index_copy(0, J, colnorm(comp, 0, m))
+        s = s.index_copy(0, J, sJ)
+    live = s > 8 * (m + p) * eps * (smax / smin)
+    s, Ht = torch.where(live, s, torch.zeros_like(s)), Ht * live.reshape(-1, 1)
+    c, order = torch.sort(c, stable=True)
+    Gt, Ht, XYt, s = Gt.index_select(0, order), Ht.index_select(0, order), XYt.index_select(0, order), s.index_select(0, order)
+    return GSVD(m, p, n, Gt, Ht, XYt[:, :n].contiguous(), XYt[:, n:].contiguous(), c, s, (sw1, sw2, sw3))
 
 
 def gemv(trans, At, m, n, x, d=None, alpha=1.0, beta=0.0, y=None):

@@ -318,6 +318,10 @@ SIGNATURES = {
     "trk_dense_svd_f64_dims": (c_int, [c_i64, c_i64, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
     "trk_dense_svd_f64": (c_int, [c_f64p, c_i64, c_i64, c_i64, c_f64p, c_i64, c_f64p, c_i64, c_f64p, c_f64p, c_i64, c_dbl, c_int,
                                   ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_stream]),
+    "trk_dense_svd_carry_f64_dims": (c_int, [c_i64, c_i64, c_i64, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
+    "trk_dense_svd_carry_f64": (c_int, [c_f64p, c_i64, c_i64, c_i64, c_f64p, c_i64, c_f64p, c_i64, c_i64, c_f64p, c_f64p, c_i64, c_dbl,
+                                        c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_stream]),
+    "trk_dense_colnorm_f64": (c_int, [c_f64p, c_i64, c_i64, c_i64, c_f64p, c_stream]),
     "trk_dense_gemv_f64": (c_int, [c_int, c_i64, c_i64, c_f64p, c_i64, c_f64p, c_f64p, c_dbl, c_dbl, c_f64p, c_stream]),
 }
 

@@ -17,6 +17,10 @@
 //     k_svd_apply   [G_I G_J] <- [G_I G_J] R and [V_I V_J] <- [V_I V_J] R for flagged pairs (one row per thread)
 //   A sweep in which no pair is flagged ends the iteration.  Then sigma_j = ||G_j|| (k_svd_colnorm); the caller sorts and
 //   scales.  Every sum has a fixed order, nothing uses atomics: two runs give the same bits.
+//
+//   The matrix rotated alongside G need not be the identity: trk_dense_svd_carry_f64 takes a companion C (nc rows, one column
+//   per column of G) from the caller and returns C times the accumulated rotation.  The rotations depend on G alone, so the
+//   plain SVD is the same driver with C = I.  The GSVD of trips_py_amd/_dense.py is two or three such runs.
 #include "trk_internal.h"
 
 #include <cfloat>
@@ -260,6 +264,16 @@ __global__ __launch_bounds__(NT) void k_svd_init(const double* __restrict__ A, i
   (void)npad;
 }
 
+// G as in k_svd_init; the companion's first n columns stay as the caller gave them, its padding columns are zeroed
+__global__ __launch_bounds__(NT) void k_svd_init_carry(const double* __restrict__ A, int64_t lda, int64_t m, int64_t n,
+                                                       double* __restrict__ G, int64_t ldg, double* __restrict__ C, int64_t ldc) {
+  const int64_t j = blockIdx.y;
+  for (int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x; i < ldg; i += (int64_t)gridDim.x * NT)
+    G[j * ldg + i] = (j < n && i < m) ? A[j * lda + i] : 0.0;
+  if (j >= n)
+    for (int64_t i = (int64_t)blockIdx.x * NT + threadIdx.x; i < ldc; i += (int64_t)gridDim.x * NT) C[j * ldc + i] = 0.0;
+}
+
 // y[j] = beta y[j] + alpha sum_i A[i, j] d[i] x[i]   (one block per column, fixed-order sum)
 __global__ __launch_bounds__(NT) void k_gemv_t64(int64_t m, const double* __restrict__ A, int64_t lda, const double* __restrict__ x,
                                                  const double* __restrict__ d, double alpha, double beta, double* __restrict__ y) {
@@ -319,32 +333,19 @@ int trk_dense_svd_f64_dims(int64_t m, int64_t n, int64_t* npad, int64_t* work_do
   return TRK_OK;
 }
 
-int trk_dense_svd_f64(const double* A, int64_t m, int64_t n, int64_t lda, double* G, int64_t ldg, double* V, int64_t ldv, double* S,
-                      double* work, int64_t work_doubles, double tol, int max_sweeps, int* sweeps, int* converged, trk_stream stream) {
-  TRK_REQUIRE(A && G && V && S && work && sweeps && converged, "trk_dense_svd_f64: NULL argument");
-  int64_t npad = 0, need = 0;
-  if (int rc = trk_dense_svd_f64_dims(m, n, &npad, &need)) return rc;
-  TRK_REQUIRE(lda >= m && ldg >= m && ldv >= npad, "trk_dense_svd_f64: leading dimensions too small (lda %lld, ldg %lld >= m %lld; "
-              "ldv %lld >= %lld)", (long long)lda, (long long)ldg, (long long)m, (long long)ldv, (long long)npad);
-  TRK_REQUIRE(work_doubles >= need, "trk_dense_svd_f64: workspace of %lld doubles, need %lld", (long long)work_doubles, (long long)need);
-  TRK_REQUIRE(max_sweeps >= 1 && tol > 0.0, "trk_dense_svd_f64: need max_sweeps >= 1 and tol > 0");
-  hipStream_t s = (hipStream_t)stream;
-  const SvdDims d = svd_dims(m, n);
+// The Jacobi iteration on G (already initialised, npad columns) with the companion C (ldc >= nc rows, npad columns) rotated
+// alongside; S[0..n) <- the column norms of G.
+static int svd_iterate(double* G, int64_t ldg, int64_t m, int64_t n, double* C, int64_t ldc, int64_t nc, double* S, double* work,
+                       const SvdDims& d, double tol, int max_sweeps, int* sweeps, int* converged, hipStream_t s) {
   double* part = work;
   double* rot = part + d.npairs * d.nchunks * P * P;
   int* flags = (int*)(rot + d.npairs * P * P);
   int* any = flags + d.rounds * d.npairs;
   int* perm = any + 1;
-
-  {
-    const int64_t span = ldg > ldv ? ldg : ldv;
-    const unsigned gx = (unsigned)((span + NT - 1) / NT < 64 ? (span + NT - 1) / NT : 64);
-    hipLaunchKernelGGL(k_svd_init, dim3(gx, (unsigned)npad), dim3(NT), 0, s, A, lda, m, n, G, ldg, npad, V, ldv);
-    TRK_LAUNCH_CHECK();
-  }
+  const int64_t npad = d.npad;
   std::vector<double> norms((size_t)n);
   std::vector<int> order((size_t)npad);
-  const int gchunks = (int)((m + NT - 1) / NT), vchunks = (int)((npad + NT - 1) / NT);
+  const int gchunks = (int)((m + NT - 1) / NT), cchunks = (int)((nc + NT - 1) / NT);
   *sweeps = 0;
   *converged = 0;
   for (int sw = 0; sw < max_sweeps; ++sw) {
@@ -363,8 +364,8 @@ int trk_dense_svd_f64(const double* A, int64_t m, int64_t n, int64_t lda, double
       TRK_LAUNCH_CHECK();
       hipLaunchKernelGGL(k_svd_jacobi, dim3((unsigned)d.npairs), dim3(NTJ), 0, s, part, (int)d.nchunks, tol, rot, fr);
       TRK_LAUNCH_CHECK();
-      hipLaunchKernelGGL(k_svd_apply, dim3((unsigned)d.npairs, (unsigned)(gchunks + vchunks)), dim3(NT), 0, s, G, ldg, m, gchunks, V,
-                         ldv, npad, perm, (int)d.nbp, r, rot, fr);
+      hipLaunchKernelGGL(k_svd_apply, dim3((unsigned)d.npairs, (unsigned)(gchunks + cchunks)), dim3(NT), 0, s, G, ldg, m, gchunks, C,
+                         ldc, nc, perm, (int)d.nbp, r, rot, fr);
       TRK_LAUNCH_CHECK();
     }
     hipLaunchKernelGGL(k_svd_any, dim3(1), dim3(NT), 0, s, flags, d.rounds * d.npairs, any);
@@ -379,6 +380,60 @@ int trk_dense_svd_f64(const double* A, int64_t m, int64_t n, int64_t lda, double
     }
   }
   hipLaunchKernelGGL(k_svd_colnorm, dim3((unsigned)n), dim3(NT), 0, s, G, ldg, m, S);
+  TRK_LAUNCH_CHECK();
+  return TRK_OK;
+}
+
+int trk_dense_svd_f64(const double* A, int64_t m, int64_t n, int64_t lda, double* G, int64_t ldg, double* V, int64_t ldv, double* S,
+                      double* work, int64_t work_doubles, double tol, int max_sweeps, int* sweeps, int* converged, trk_stream stream) {
+  TRK_REQUIRE(A && G && V && S && work && sweeps && converged, "trk_dense_svd_f64: NULL argument");
+  int64_t npad = 0, need = 0;
+  if (int rc = trk_dense_svd_f64_dims(m, n, &npad, &need)) return rc;
+  TRK_REQUIRE(lda >= m && ldg >= m && ldv >= npad, "trk_dense_svd_f64: leading dimensions too small (lda %lld, ldg %lld >= m %lld; "
+              "ldv %lld >= %lld)", (long long)lda, (long long)ldg, (long long)m, (long long)ldv, (long long)npad);
+  TRK_REQUIRE(work_doubles >= need, "trk_dense_svd_f64: workspace of %lld doubles, need %lld", (long long)work_doubles, (long long)need);
+  TRK_REQUIRE(max_sweeps >= 1 && tol > 0.0, "trk_dense_svd_f64: need max_sweeps >= 1 and tol > 0");
+  hipStream_t s = (hipStream_t)stream;
+  {
+    const int64_t span = ldg > ldv ? ldg : ldv;
+    const unsigned gx = (unsigned)((span + NT - 1) / NT < 64 ? (span + NT - 1) / NT : 64);
+    hipLaunchKernelGGL(k_svd_init, dim3(gx, (unsigned)npad), dim3(NT), 0, s, A, lda, m, n, G, ldg, npad, V, ldv);
+    TRK_LAUNCH_CHECK();
+  }
+  return svd_iterate(G, ldg, m, n, V, ldv, npad, S, work, svd_dims(m, n), tol, max_sweeps, sweeps, converged, s);
+}
+
+int trk_dense_svd_carry_f64_dims(int64_t m, int64_t n, int64_t nc, int64_t* npad, int64_t* work_doubles) {
+  TRK_REQUIRE(nc >= 1, "trk_dense_svd_carry_f64_dims: the companion needs at least one row (got %lld)", (long long)nc);
+  return trk_dense_svd_f64_dims(m, n, npad, work_doubles);
+}
+
+int trk_dense_svd_carry_f64(const double* A, int64_t m, int64_t n, int64_t lda, double* G, int64_t ldg, double* C, int64_t nc,
+                            int64_t ldc, double* S, double* work, int64_t work_doubles, double tol, int max_sweeps, int* sweeps,
+                            int* converged, trk_stream stream) {
+  TRK_REQUIRE(A && G && C && S && work && sweeps && converged, "trk_dense_svd_carry_f64: NULL argument");
+  int64_t npad = 0, need = 0;
+  if (int rc = trk_dense_svd_carry_f64_dims(m, n, nc, &npad, &need)) return rc;
+  TRK_REQUIRE(lda >= m && ldg >= m && ldc >= nc, "trk_dense_svd_carry_f64: leading dimensions too small (lda %lld, ldg %lld >= m "
+              "%lld; ldc %lld >= nc %lld)", (long long)lda, (long long)ldg, (long long)m, (long long)ldc, (long long)nc);
+  TRK_REQUIRE(work_doubles >= need, "trk_dense_svd_carry_f64: workspace of %lld doubles, need %lld", (long long)work_doubles,
+              (long long)need);
+  TRK_REQUIRE(max_sweeps >= 1 && tol > 0.0, "trk_dense_svd_carry_f64: need max_sweeps >= 1 and tol > 0");
+  hipStream_t s = (hipStream_t)stream;
+  {
+    const int64_t span = ldg > ldc ? ldg : ldc;
+    const unsigned gx = (unsigned)((span + NT - 1) / NT < 64 ? (span + NT - 1) / NT : 64);
+    hipLaunchKernelGGL(k_svd_init_carry, dim3(gx, (unsigned)npad), dim3(NT), 0, s, A, lda, m, n, G, ldg, C, ldc);
+    TRK_LAUNCH_CHECK();
+  }
+  return svd_iterate(G, ldg, m, n, C, ldc, nc, S, work, svd_dims(m, n), tol, max_sweeps, sweeps, converged, s);
+}
+
+int trk_dense_colnorm_f64(const double* X, int64_t ldx, int64_t rows, int64_t cols, double* out, trk_stream stream) {
+  TRK_REQUIRE(X && out, "trk_dense_colnorm_f64: NULL argument");
+  TRK_REQUIRE(rows >= 1 && cols >= 1 && ldx >= rows, "trk_dense_colnorm_f64: bad shape %lld x %lld (ldx %lld)", (long long)rows,
+              (long long)cols, (long long)ldx);
+  hipLaunchKernelGGL(k_svd_colnorm, dim3((unsigned)cols), dim3(NT), 0, (hipStream_t)stream, X, ldx, rows, out);
   TRK_LAUNCH_CHECK();
   return TRK_OK;
 }

@@ -11,6 +11,10 @@ and the dense SVD of the direct solvers (tSVD, Tikhonov): the float64 one-sided 
 
     svd(A)                           -> (U m x k, S k, Vh k x n), k = min(m, n), S descending (np.linalg.svd(full_matrices=False))
 
+and the generalised SVD of tGSVD_sol (:257-271), three runs of the same Jacobi iteration (docs/kernels/dense_svd.md, "GSVD"):
+
+    gsvd(A, B)                       -> (U m x n, V p x n, X n x n, C n x n, S n x n): A = U C X^T, B = V S X^T
+
 The `*_update` functions accept either the reference's arrays (NumPy, n x k) — then the bases are uploaded, one step is
 taken and NumPy arrays come back, O(k n) traffic like the reference's own hstack — or the handles they returned the
 previous time (`KrylovArrays`), in which case the bases stay on the GPU and the step costs two operator applies.
@@ -195,3 +199,28 @@ def svd(A, max_sweeps=None):
     if isinstance(A, torch.Tensor):
         return Ut.T, S, Vt
     return Ut.T.cpu().numpy(), S.cpu().numpy(), Vt.cpu().numpy()
+
+
+def gsvd(A, B):
+    """Generalised SVD of A (m x n) and B (p x n), m >= n, p >= n, [A; B] of full column rank: A = U C X^T, B = V S X^T with
+    C = diag(c), S = diag(s), c ascending, C^2 + S^2 = I, X n x n invertible, and the columns of U (m x n) and V (p x n)
+    orthonormal — the reference's return order and shapes (it also demands m == p; nothing here needs that).
+
+    A column of U whose c <= n eps, or of V whose s <= n eps, is ZERO: that direction is not determined by the pair, and where the
+    reference returns some orthonormal completion this returns nothing, as `svd` does for a zero singular value.
+
+    A, B: NumPy array, np.matrix, scipy.sparse matrix, an engine operator (densified through todense()) or a torch tensor.  NumPy
+    arrays come back for host inputs, float64 device tensors when A is a torch tensor.  ValueError for shapes outside the above
+    (raised before the device is touched) and for a pair whose [A; B] has no full column rank."""
+    return gsvd_factors(A, B)[0]
+
+
+def gsvd_factors(A, B):
+    """(gsvd(A, B), the _dense.GSVD it was made from: the unnormalised factors, Y = X^-T and the sweep counts)."""
+    from . import _dense
+    _dense.gsvd_shapes(A, B)
+    f = _dense.gsvd_device(A, B)
+    out = (f.Ut().T, f.Vt().T, f.Xt.T, torch.diag(f.c), torch.diag(f.s))
+    if isinstance(A, torch.Tensor):
+        return out, f
+    return tuple(t.cpu().numpy() for t in out), f

@@ -1,4 +1,4 @@
-"""Krylov / projection solvers and the dense direct solvers (tSVD, Tikhonov) with the reference's signatures
+"""Krylov / projection solvers and the dense direct solvers (tSVD, tGSVD, Tikhonov) with the reference's signatures
 (trips/solvers/*.py), running on the HIP engine."""
 from .CGLS import CGLS, CGLSRun, CGLSRunFused, CGLSRunSharded  # noqa: F401
 from .Hybrid_LSQR import Hybrid_LSQR  # noqa: F401
@@ -9,4 +9,5 @@ from .GK_Tikhonov import Golub_Kahan_Tikhonov  # noqa: F401
 from .A_Tikhonov import Arnoldi_Tikhonov  # noqa: F401
 from .GMRES import GMRES  # noqa: F401
 from .tSVD import tSVD_sol  # noqa: F401
+from .tGSVD import tGSVD_sol  # noqa: F401
 from .Tikhonov import Tikhonov  # noqa: F401
