@@ -119,6 +119,17 @@ int trk_csr_create(int64_t nrows, int64_t ncols, int64_t nnz, const int64_t* ind
                    const float* values_host, const int64_t* t_indptr_host, const int* t_indices_host,
                    const float* t_values_host, trk_op** out);
 
+/* Separable band operator y = vec_F(W_n X W_m^T), X = x.reshape(n, m, order='F'), and its transpose x = vec_F(W_n^T Y W_m): the
+ * framelet analysis operator (operators.py:50-113) applied matrix-free by stencil kernels (csrc/framelet2d.hip).  W_n is
+ * (blocks_n n) x n, W_m is (blocks_m m) x m; y[p + blocks_n n q] with p = b n + i, q = c m + j (the layout of the CSR form of
+ * kron(W_m, W_n)).  band_n[b][i][t] = W_n[b n + i, i - half_n + t], t = 0 .. 2 half_n, 0 where that column lies outside [0, n);
+ * band_m likewise (host float64, rounded once to float32 here).  The interior rows half <= i <= n - 1 - half of every block must be
+ * one stencil, shifted (compared as float32) and out-of-matrix entries 0: TRK_EINVAL otherwise.  A half-width above 7 (framelet
+ * levels above 4): TRK_EUNSUPPORTED.  Both checks come before any device work.  trk_op_shape reports
+ * (blocks_n n blocks_m m, n m); batch, ldx, ldy and sumsq_dev of trk_op_apply are honoured; no fused forms (trk_op_axpby_caps: 0). */
+int trk_framelet2d_create(int n, int m, int blocks_n, int half_n, const double* band_n, int blocks_m, int half_m,
+                          const double* band_m, trk_op** out);
+
 /* Block-diagonal operator over frames (pylops.BlockDiag at io.py:420; sparse slicing :223-225).
  * The handle borrows `ops` (they must outlive it). x and y are frame-major. */
 int trk_blockdiag_create(trk_op* const* ops, int count, trk_op** out);

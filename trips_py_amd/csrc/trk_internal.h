@@ -438,7 +438,7 @@ struct PostReq {
 
 // ------------------------------------------------------------------ operator handle
 struct trk_op {
-  int kind;  // 1 blur2d, 2 radon2d, 3 deriv2d, 4 spacetime, 5 blockdiag
+  int kind;  // 1 blur2d, 2 radon2d, 3 deriv2d, 4 spacetime, 5 blockdiag, 6 csr, 7 fanbeam2d, 8 framelet2d
   int64_t rows, cols;
   void* impl;
   int (*apply)(trk_op*, int transpose, const float* x, int64_t ldx, float* y, int64_t ldy, int batch,

@@ -550,10 +550,9 @@ class SparseBlockDiag(SparseOp):
         return cls(AA[lo:hi], engine=engine)
 
 
-def create_framelet_operator(n, m, l, engine=None):
-    """The reference's framelet analysis operator (trips/utilities/operators.py:50-113) as ONE sparse matrix on the device:
-    vec_F(W_n X W_m^H) = kron(W_m, W_n) vec_F(X) for the reference's column-major reshapes (:106-108); rows
-    n(2l+1) * m(2l+1), columns n*m."""
+def framelet_analysis_matrix(n, l):
+    """The reference's 1-D framelet analysis matrix W_n of level l as a scipy CSR matrix, (2l+1) n x n
+    (trips/utilities/operators.py:50-103, recursion as written there: the deepest level comes back without the low-pass product)."""
     import scipy.sparse as sp
 
     def construct_H(lev, nn):                       # operators.py:50-85
@@ -576,7 +575,114 @@ def create_framelet_operator(n, m, l, engine=None):
         H0, H1, H2 = construct_H(level, nn)
         return sp.vstack((analysis(nn, level + 1, H0), H1, H2)) * w
 
-    W_n, W_m = analysis(n, 1, 1), analysis(m, 1, 1)
+    return sp.csr_matrix(analysis(n, 1, 1))
+
+
+def band_tables(W, n, half=None):
+    """A 1-D analysis matrix W (blocks n x n, dense or scipy.sparse) as the band tables of trk_framelet2d_create:
+    (blocks, half, band) with band[b, i, t] = W[b n + i, i - half + t], 0 where that column lies outside [0, n), float64.
+    half=None: the largest |column - (row mod n)| over W's non-zeros.  Pure NumPy.  ValueError: W has not n columns, its row count is
+    no multiple of n, a non-zero lies outside the band of a given `half`, or an interior row of a block (half <= i <= n - 1 - half)
+    is not the block's stencil shifted (compared as float32, the precision of the kernels): no separable band operator of this kind."""
+    n = int(n)
+    if hasattr(W, "tocoo"):
+        C = W.tocoo()
+        shape, r, c, v = C.shape, np.asarray(C.row, dtype=np.int64), np.asarray(C.col, dtype=np.int64), np.asarray(C.data, dtype=np.float64)
+    else:
+        D = np.asarray(W, dtype=np.float64)
+        if D.ndim != 2:
+            raise ValueError("band_tables: a 2-D matrix expected")
+        shape = D.shape
+        r, c = np.nonzero(D)
+        v = D[r, c]
+    if n < 1 or shape[1] != n or shape[0] % n or shape[0] == 0:
+        raise ValueError(f"band_tables: a {shape[0]} x {shape[1]} matrix is not (blocks * {n}) x {n}")
+    keep = v != 0
+    r, c, v = r[keep], c[keep], v[keep]
+    blocks = shape[0] // n
+    i = r % n
+    reach = int(np.abs(c - i).max()) if v.size else 0
+    if half is None:
+        half = reach
+    elif reach > int(half):
+        k = int(np.argmax(np.abs(c - i)))
+        raise ValueError(f"band_tables: W[{r[k]}, {c[k]}] is non-zero, {reach} off the diagonal of its block: outside the band of half-width {half}")
+    half = int(half)
+    band = np.zeros((blocks, n, 2 * half + 1))
+    np.add.at(band, (r // n, i, c - i + half), v)
+    return blocks, half, _check_band(band, n, half)
+
+
+def _check_band(band, n, half):
+    """band_tables' structure checks on the finished table (the library repeats them on what it is handed)."""
+    blocks, w = band.shape[0], 2 * half + 1
+    if band.shape != (blocks, n, w):
+        raise ValueError(f"band table of shape {band.shape}, expected {(blocks, n, w)}")
+    cols = np.arange(n)[:, None] - half + np.arange(w)[None, :]
+    if np.any(band[:, (cols < 0) | (cols >= n)] != 0):
+        raise ValueError("band table: a non-zero entry lies outside the band's part inside the matrix")
+    if n > 2 * half:
+        inner = band[:, half:n - half, :].astype(np.float32)
+        if np.any(inner != inner[:, :1, :]):
+            raise ValueError("band table: the interior rows of a block are not one shifted stencil")
+    return band
+
+
+class Framelet2D(_HandleOperator):
+    """A separable band operator: y = vec_F(W_n X W_m^T) for X = x.reshape(n, m, order='F'), `.T` its exact transpose, applied
+    matrix-free by the stencil kernels of csrc/framelet2d.hip; rows blocks_n n * blocks_m m, columns n m, the layout of the CSR form
+    of kron(W_m, W_n).  Framelet2D(n, m, l) is the reference's framelet analysis operator of level l
+    (trips/utilities/operators.py:50-113, create_framelet_operator); Framelet2D.from_analysis takes any pair of 1-D matrices whose
+    blocks are band matrices with one stencil in their interior rows (boundary rows are free).  Levels 1 .. 4 (half-width <= 7)."""
+
+    MAX_HALF = 7            # csrc/framelet2d.hip: kMaxHalf
+    streaming = True
+
+    def __init__(self, n, m, l, engine=None):
+        n, m, l = int(n), int(m), int(l)
+        if l < 1:
+            raise ValueError("Framelet2D: level l >= 1 expected")
+        self._setup(framelet_analysis_matrix(n, l), framelet_analysis_matrix(m, l) if m != n else None, n, m, engine, l)
+
+    @classmethod
+    def from_analysis(cls, W_n, W_m, n, m, engine=None):
+        """From 1-D analysis matrices W_n ((blocks_n n) x n) and W_m ((blocks_m m) x m), dense or scipy.sparse."""
+        self = cls.__new__(cls)
+        self._setup(W_n, W_m, int(n), int(m), engine, None)
+        return self
+
+    def _setup(self, W_n, W_m, n, m, engine, l):
+        tn = band_tables(W_n, n)
+        tm = tn if W_m is None else band_tables(W_m, m)
+        self.n, self.m, self.l = n, m, l
+        self.blocks_n, self.half_n, self.blocks_m, self.half_m = tn[0], tn[1], tm[0], tm[1]
+        if max(tn[1], tm[1]) > self.MAX_HALF:
+            raise ValueError(f"Framelet2D: half-widths {tn[1]}, {tm[1]} of the 1-D factors exceed the stencil kernels' limit of {self.MAX_HALF} "
+                             f"(framelet levels 1 .. 4); use create_framelet_operator(..., matrix_free=False) for the CSR form")
+        engine = engine if engine is not None else default_engine()
+        h = self._create(engine, n, m, tn, tm)
+        super().__init__(h, engine)
+
+    @staticmethod
+    def _create(engine, n, m, tn, tm):
+        """trk_framelet2d_create on (blocks, half, band) triples; the library's own checks raise ValueError / NotImplementedError."""
+        an, pn = _dbl_array(tn[2])
+        am, pm = _dbl_array(tm[2])
+        h = ctypes.c_void_p()
+        _lib.check(engine.lib.trk_framelet2d_create(n, m, int(tn[0]), int(tn[1]), pn, int(tm[0]), int(tm[1]), pm, ctypes.byref(h)),
+                   "trk_framelet2d_create")
+        return h
+
+
+def create_framelet_operator(n, m, l, engine=None, matrix_free=False):
+    """The reference's framelet analysis operator (trips/utilities/operators.py:50-113): vec_F(W_n X W_m^H) = kron(W_m, W_n) vec_F(X)
+    for the reference's column-major reshapes (:106-108); rows n(2l+1) * m(2l+1), columns n*m.
+    matrix_free=False: ONE sparse matrix on the device (SparseOp; 169 non-zeros per pixel at l = 2, 1764 at l = 3).
+    matrix_free=True: Framelet2D, the two 1-D band matrices applied by stencil kernels — the form for images beyond ~1024^2."""
+    if matrix_free:
+        return Framelet2D(n, m, l, engine=engine)
+    import scipy.sparse as sp
+    W_n, W_m = framelet_analysis_matrix(n, l), framelet_analysis_matrix(m, l)
     return SparseOp(sp.kron(W_m, W_n, format="csr"), engine=engine)
 
 
