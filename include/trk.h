@@ -843,6 +843,11 @@ int trk_cgls_iterate_sharded(trk_op* A, trk_comm* comm, int k_first, int n_iters
  *   (at most max_sweeps; the last one is the sweep that found every pair orthogonal), *converged = 1 when that sweep happened.
  *   Bitwise reproducible (fixed summation orders, no atomics).  Two host synchronisations per sweep (the column order by norm, the
  *   sweep's verdict).
+ *   Range: the iteration squares entries and is not scaled here.  The entries of A must be finite, and the squares of the nonzero
+ *   ones, summed down a column, must neither overflow nor underflow: a matrix whose largest |entry| lies within 2^+-400 of 1
+ *   is safe for any m.  Outside that range the Gram matrices are Inf or all zero, and with a NaN every comparison is false: the
+ *   call then reports *converged = 1 on a wrong answer.  Scaling A by a power of two first (and S back) removes the limit and
+ *   changes no other bit of the result; trips_py_amd/_dense.py does that, and refuses a NaN or Inf, for both entry points.
  * trk_dense_svd_carry_f64 (and its _dims): the same iteration, but the matrix rotated alongside G is the caller's companion C
  *   (nc >= 1 rows, ldc >= nc, npad columns) instead of the identity: its first n columns are read as given, columns n..npad are
  *   zeroed by the call, and C times the accumulated rotation comes back.  The rotations depend on A alone, so G, S, *sweeps and

@@ -5,6 +5,7 @@ built on it, and the two float64 products (trk_dense_gemv_f64).
 A device matrix is held as a torch float64 tensor `At` of shape (n, m), contiguous: row j of `At` is column j of the m x n matrix,
 i.e. the column-major layout the kernels read (leading dimension m)."""
 import ctypes
+import math
 import warnings
 
 import numpy as np
@@ -55,10 +56,39 @@ def to_device_t(A, role="A"):
     return At, int(At.shape[1]), int(At.shape[0])
 
 
-def _svd_tall(At, m, n, max_sweeps=MAX_SWEEPS):
+def amax_finite(Xt, role):
+    """The largest |entry| of a device matrix as a host float (one synchronisation); ValueError naming `role` when the matrix
+    holds a NaN or an Inf, which no sweep of the Jacobi iteration would notice: every comparison with a NaN is false, so the
+    iteration reports convergence."""
+    amax = float(Xt.abs().max()) if Xt.numel() else 0.0
+    if not np.isfinite(amax):
+        raise ValueError(f"dense SVD: the matrix {role} has a NaN or Inf entry")
+    return amax
+
+
+def pow2_exponent(amax):
+    """e with amax in [2^e, 2^(e + 1)); 0 for amax = 0."""
+    return math.frexp(amax)[1] - 1 if amax > 0.0 else 0
+
+
+def scale_pow2(X, k):
+    """X * 2^k, exact (short of the ends of the float64 range).  In two factors: 2^k itself leaves the range for |k| > 1023."""
+    if k == 0:
+        return X
+    h = k // 2
+    return (X * math.ldexp(1.0, h)) * math.ldexp(1.0, k - h)
+
+
+def _svd_tall(At, m, n, max_sweeps=MAX_SWEEPS, role="A", amax=None):
     """One-sided Jacobi on the m x n (m >= n) column-major At -> (Ut (n, m), S (n,), Vt (n, n), sweeps), sorted descending:
-    row j of Ut / Vt is the j-th left / right singular vector."""
+    row j of Ut / Vt is the j-th left / right singular vector.
+
+    The kernels square entries, so the iteration runs on At scaled by the power of two that brings its largest |entry| (`amax`;
+    taken here when not given) into [1, 2), and S is scaled back: exact, and the factors of 2^k A are those of A bit for bit
+    with S times 2^k.  ValueError for a matrix with a NaN or Inf entry."""
     eng = _engine()
+    e = pow2_exponent(amax_finite(At, role) if amax is None else amax)
+    At = scale_pow2(At, -e).contiguous()
     lib = eng.lib
     npad, need = ctypes.c_int64(0), ctypes.c_int64(0)
     _lib.check(lib.trk_dense_svd_f64_dims(m, n, ctypes.byref(npad), ctypes.byref(need)), "trk_dense_svd_f64_dims")
@@ -79,30 +109,33 @@ def _svd_tall(At, m, n, max_sweeps=MAX_SWEEPS):
     inv = torch.where(S > 0, 1.0 / torch.where(S > 0, S, torch.ones_like(S)), torch.zeros_like(S))
     Ut = Gt * inv.reshape(-1, 1)
     Vt = V[:n, :n].index_select(0, perm)          # row j of V^T = column perm[j] of V (V is column-major: row = column)
-    return Ut, S, Vt.contiguous(), sweeps.value
+    return Ut, scale_pow2(S, e), Vt.contiguous(), sweeps.value
 
 
-def svd_device(A, max_sweeps=MAX_SWEEPS):
+def svd_device(A, max_sweeps=MAX_SWEEPS, role="A"):
     """Thin SVD of A on the device: (Ut (k, m), S (k,), Vt (k, n), sweeps) as float64 device tensors, k = min(m, n), singular values
-    descending; A = Ut^T diag(S) Vt.  A wide matrix runs on A^T with the factors swapped."""
-    At, m, n = to_device_t(A)
-    return svd_device_t(At, m, n, max_sweeps)
+    descending; A = Ut^T diag(S) Vt.  A wide matrix runs on A^T with the factors swapped.  Any finite float64 matrix is accepted
+    (see _svd_tall); ValueError naming `role` for one with a NaN or Inf entry."""
+    At, m, n = to_device_t(A, role)
+    return svd_device_t(At, m, n, max_sweeps, role)
 
 
-def svd_device_t(At, m, n, max_sweeps=MAX_SWEEPS):
+def svd_device_t(At, m, n, max_sweeps=MAX_SWEEPS, role="A"):
     if min(m, n) > MAX_COLS:
         raise ValueError(f"dense SVD: at most {MAX_COLS} columns (of the matrix or of its transpose); got {m} x {n}")
     if m >= n:
-        return _svd_tall(At, m, n, max_sweeps)
-    Ut, S, Vt, sw = _svd_tall(At.T.contiguous(), n, m, max_sweeps)   # A^T = U' S V'^T  ->  A = V' S U'^T
+        return _svd_tall(At, m, n, max_sweeps, role)
+    Ut, S, Vt, sw = _svd_tall(At.T.contiguous(), n, m, max_sweeps, role)   # A^T = U' S V'^T  ->  A = V' S U'^T
     return Vt, S, Ut, sw
 
 
 def svd_carry_t(At, m, n, Ct, max_sweeps=MAX_SWEEPS):
     """One-sided Jacobi on the m x n (m >= n) column-major At with a carried companion (trk_dense_svd_carry_f64): Ct is (n, nc),
     row j the companion's column j.  With W the accumulated rotation, returns (Gt (n, m) = (A W)^T, S (n,) = its column norms,
-    (C W)^T (n, nc), sweeps) — in the order of A's columns, neither sorted nor normalised."""
+    (C W)^T (n, nc), sweeps) — in the order of A's columns, neither sorted nor normalised.  As in _svd_tall the iteration runs
+    on At scaled by a power of two to a largest |entry| in [1, 2), and Gt and S are scaled back; ValueError for a NaN or Inf."""
     eng = _engine()
+    e = pow2_exponent(amax_finite(At, "A"))
     lib = eng.lib
     nc = int(Ct.shape[1])
     if tuple(At.shape) != (n, m) or int(Ct.shape[0]) != n:
@@ -110,7 +143,7 @@ def svd_carry_t(At, m, n, Ct, max_sweeps=MAX_SWEEPS):
     npad, need = ctypes.c_int64(0), ctypes.c_int64(0)
     _lib.check(lib.trk_dense_svd_carry_f64_dims(m, n, nc, ctypes.byref(npad), ctypes.byref(need)), "trk_dense_svd_carry_f64_dims")
     npad = npad.value
-    At = At.contiguous()
+    At = scale_pow2(At, -e).contiguous()
     G = torch.empty((npad, m), dtype=torch.float64, device=eng.device)
     C = torch.empty((npad, nc), dtype=torch.float64, device=eng.device)
     C[:n].copy_(Ct)
@@ -123,7 +156,7 @@ def svd_carry_t(At, m, n, Ct, max_sweeps=MAX_SWEEPS):
                                            ctypes.byref(conv), eng.stream()), "trk_dense_svd_carry_f64")
     if not conv.value:
         warnings.warn(f"dense SVD: {m} x {n} not converged after {sweeps.value} Jacobi sweeps", RuntimeWarning)
-    return G[:n], S, C[:n], sweeps.value
+    return scale_pow2(G[:n], e), scale_pow2(S, e), C[:n], sweeps.value
 
 
 def colnorm(Xt, row0, rows):
@@ -198,7 +231,8 @@ def gsvd_device(A, L, max_sweeps=MAX_SWEEPS):
     At, _, _ = to_device_t(A, "A")
     Lt, _, _ = to_device_t(L, "L")
     eps = np.finfo(np.float64).eps
-    Qt, sig, Vmt, sw1 = _svd_tall(torch.cat((At, Lt), dim=1), m + p, n, max_sweeps)
+    amax = max(amax_finite(At, "A"), amax_finite(Lt, "L"))
+    Qt, sig, Vmt, sw1 = _svd_tall(torch.cat((At, Lt), dim=1), m + p, n, max_sweeps, "[A; L]", amax)
     smax, smin = float(sig[0]), float(sig[-1])
     if not smin > max(m + p, n) * eps * smax:
         raise ValueError(f"gsvd: [A; L] has no full column rank to working precision (sigma_min = {smin:.3e}, sigma_max = "

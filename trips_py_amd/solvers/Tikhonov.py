@@ -36,7 +36,7 @@ def _standard_form(At, m, n, L, bv):
         raise ValueError(f"Tikhonov: L has {Lh.shape[1]} columns, A has {n}")
     if Lh.shape[0] < n:
         Lh = np.vstack((Lh, np.zeros((n - Lh.shape[0], n))))
-    _, SL, WLt, _ = _dense.svd_device(Lh)
+    _, SL, WLt, _ = _dense.svd_device(Lh, role="L")
     tol = max(Lh.shape) * np.finfo(np.float64).eps * float(SL[0]) if SL.numel() else 0.0
     r = int((SL > tol).sum())
     Rp_t = WLt[:r] / SL[:r].reshape(-1, 1)                 # (r, n): rows = columns of R^+ = W_r diag(1/s_r)
