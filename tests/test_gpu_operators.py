@@ -127,10 +127,11 @@ def test_radon_vs_oracle_convention(N, na, nd):
 
 
 @pytest.mark.parametrize("case", ["fan7", "scattered", "wide_detector", "narrow_detector", "near45", "quads", "signs", "twice", "deg180"])
-def test_radon_shared_window_forward_vs_oracle(case):
-    """N >= 1024 runs the window-sharing forward kernel (4 neighbouring angles stage one LDS window; rays are owned by
-    their column at the band's top row).  Against the oracle's sparse Joseph matrix, including what the kernel special-
-    cases: a last group of fewer than 4 angles, groups mixing row- and column-driven angles, angles in scattered order
+def test_radon_shared_window_forward_vs_oracle(case, monkeypatch):
+    """The quad forward kernels k_radon_fwd_quadf / k_radon_fwd_quad (4 neighbouring quads stage one LDS window; rays are owned by
+    their column at the band's top row), which a 1024^2 handle takes once the band-resident kernel is switched off
+    (TRK_RADON_NO_BANDRES=1, read when the handle is made).  Against the oracle's sparse Joseph matrix, including what the kernels
+    special-case: a last group of fewer than 4 quads, groups mixing row- and column-driven angles, angles in scattered order
     (the union window does not fit -> direct gathers), detectors wider / narrower than the image."""
     from oracle import cpu_ref as O
     from trips_py_amd.operators import Radon2DParallel
@@ -147,7 +148,9 @@ def test_radon_shared_window_forward_vs_oracle(case):
            "twice": np.deg2rad([30.0, 30.0, 150.0, 60.0, 30.0, 120.0]),
            "deg180": np.linspace(0, np.pi, 180, endpoint=False)}[case]
     nd = {"wide_detector": 1500, "narrow_detector": 700}.get(case, N)
+    monkeypatch.setenv("TRK_RADON_NO_BANDRES", "1")
     R, Ro = Radon2DParallel(N, ang, n_det=nd), O.Radon2D(N, ang, n_det=nd)
+    monkeypatch.delenv("TRK_RADON_NO_BANDRES")
     rng = np.random.default_rng(11)
     ii, jj = np.meshgrid(np.arange(N), np.arange(N), indexing="ij")
     x = (np.exp(-((ii - N / 2.5) ** 2 + (jj - N / 1.7) ** 2) / (0.02 * N * N)) + 0.05 * rng.random((N, N))).reshape(-1)
@@ -173,7 +176,8 @@ def test_radon_lean_quad_kernel_equals_the_round4_kernel_bit_for_bit(case, monke
     the plan allows, k_radon_fwd_quad the listed rest.  Both own the same rays and add the same products in the same order, so the
     sinogram must not change by a bit against the all-k_radon_fwd_quad run (TRK_RADON_NO_QUADF=1) — on full 1-degree sets (every
     workgroup lean but ragged ones), incomplete quads, scattered angles (windows that do not fit: listed), an image whose bands are
-    ragged, a detector wider than the image and a dynamic operator (frames of few angles)."""
+    ragged, a detector wider than the image and a dynamic operator (frames of few angles).  The handles are made with
+    TRK_RADON_NO_BANDRES=1: at 1024^2 the band-resident kernel would otherwise take the forward and neither quad kernel would run."""
     from trips_py_amd.operators import Radon2DParallel
     N = 1028 if case == "ragged1028" else 1024
     ang = {"deg180": np.linspace(0, np.pi, 180, endpoint=False),
@@ -184,11 +188,13 @@ def test_radon_lean_quad_kernel_equals_the_round4_kernel_bit_for_bit(case, monke
            "wide_detector": np.linspace(0, np.pi, 36, endpoint=False),
            "dynamic": np.deg2rad(np.arange(2)[:, None] * 7.0 + 12.0 * np.arange(15)[None, :])}[case]
     nd = 1500 if case == "wide_detector" else N
+    monkeypatch.setenv("TRK_RADON_NO_BANDRES", "1")
     if case == "dynamic":                            # two frames of 15 angles each: ONE handle, one launch (BlockDiagOp)
         from trips_py_amd.operators import BlockDiagOp
         R = BlockDiagOp([Radon2DParallel(N, a, n_det=nd) for a in ang])
     else:
         R = Radon2DParallel(N, ang, n_det=nd)
+    monkeypatch.delenv("TRK_RADON_NO_BANDRES")
     eng = R.engine
     g = torch.Generator(device=eng.device).manual_seed(5)
     x = torch.rand(R.shape[1], device=eng.device, generator=g)
@@ -375,13 +381,16 @@ def test_dynamic_radon_equals_blockdiag_of_frames(N, nt, na):
     assert relerr(F @ x, Fo @ f(x)) < 1e-5 and relerr(F.T @ y, Fo.T @ f(y)) < 1e-5
 
 
-def test_dynamic_radon_large_frames_use_the_shared_window_kernel():
-    """Frames of 1024^2 (window-sharing forward kernel, frame-major angle groups): one dynamic handle == per-frame handles."""
+def test_dynamic_radon_large_frames_use_the_shared_window_kernel(monkeypatch):
+    """Frames of 1024^2 on the quad forward kernels (k_radon_fwd_quadf / k_radon_fwd_quad, frame-major quad groups; the handles are
+    made with TRK_RADON_NO_BANDRES=1, or the band-resident kernel would take them): one dynamic handle == per-frame handles."""
     from trips_py_amd.operators import BlockDiagOp, Radon2DParallel
     N, nt, na = 1024, 2, 5
     angs = [np.deg2rad(3.0 * t + 36.0 * np.arange(na)) for t in range(nt)]
+    monkeypatch.setenv("TRK_RADON_NO_BANDRES", "1")
     frames = [Radon2DParallel(N, a) for a in angs]
     F = BlockDiagOp(frames)
+    monkeypatch.delenv("TRK_RADON_NO_BANDRES")
     x = np.random.default_rng(4).random(nt * N * N)
     per_f = np.concatenate([frames[t] @ x[t * N * N:(t + 1) * N * N] for t in range(nt)])
     assert np.array_equal(F @ x, per_f)

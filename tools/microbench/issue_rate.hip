@@ -4,7 +4,7 @@
 // throughput at more than one wave per SIMD ("one wave alone: 4").  This program measures, on the chip, at the clock the
 // chip holds, for 1 / 2 / 4 / 7 waves per SIMD:
 //   * independent v_fma_f32, v_add_u32, v_and_b32, v_lshrrev_b32, v_cvt_f32_u32, v_pk_fma_f32 streams,
-//   * the forward projector's 7-instruction march (k_radon_fwd_win, radon2d.hip) without its LDS read,
+//   * the forward projector's 7-instruction march (k_radon_fwd_lds, radon_fwd.hip; what bounds it: docs/kernels/radon.md 4.4c) without its LDS read,
 //   * the same march WITH its ds_read2_b32 tap, for ray spacings inv = 1.0 (conflict-free), 1.2, 1.414 columns per lane,
 //   * the bare LDS taps: ds_read2_b32, ds_read_b64 (pair layout), and dword-aligned (i.e. MISALIGNED) ds_read_b64 /
 //     ds_read_b128 — first checked for what they return, then timed.

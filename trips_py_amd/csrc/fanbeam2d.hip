@@ -259,7 +259,7 @@ __global__ __launch_bounds__(256) void k_fan_fwd_march(const float* __restrict__
   else part[(int64_t)blockIdx.y * nrays + ray] = acc0 + acc1;
 }
 
-// Band-resident forward march (small images; round 5, as k_radon_fwd_band of radon2d.hip): a 64-row band of a 512-wide image is
+// Band-resident forward march (small images; round 5, as k_radon_fwd_band of radon_fwd.hip): a 64-row band of a 512-wide image is
 // 130 KB and fits the LDS of one CU.  k_fan_fwd_march takes its two taps per step with one scattered 8-byte load per lane, and the
 // texture addresser's rate for such loads (16.6 cycles per wave-load) IS its time (28 of 37 us at 512^2 x 180 x 724), behind a launch
 // that makes two padded copies of the image.  Here a workgroup of 16 waves loads its band once — rows of the image for the steep rays,
@@ -525,7 +525,7 @@ __global__ __launch_bounds__(256) void k_fan_adj_march(float* __restrict__ img,
   auto fetch = [&](int a, int d) -> FanRec {
     const u4f t = __builtin_bit_cast(u4f, __builtin_amdgcn_raw_buffer_load_b128(rsrc, (d + FAN_RP) << 4, a * ndp * 16, 0));
     // (elements copied to scalars first: __builtin_bit_cast(float, t[k]) on an ext-vector ELEMENT reads element 0 whatever k is —
-    //  hipcc / ROCm 7.2, met before in radon2d.hip's adj_gather)
+    //  hipcc / ROCm 7.2, met before in radon_adj.hip's adj_gather)
     const unsigned t0 = t[0], t1 = t[1], t2 = t[2], t3 = t[3];
     return FanRec{t0, __builtin_bit_cast(float, t1), (int)t2, __builtin_bit_cast(float, t3)};
   };

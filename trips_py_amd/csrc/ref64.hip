@@ -8,7 +8,7 @@
 //                    operator's weights bit for bit, summed in float64 instead of fp32.
 //     One thread per ray (forward) / per pixel (adjoint, gather over the rays that touch it: matched to the forward tap by tap).
 //   * the vector kernels of a Golub-Kahan half step on the element type: out = a Op(x) + b z (float64 coefficients and
-//     products, ONE rounding to T — the arithmetic of the production projector's epilogue, radon2d.hip epi_combine) with the fused
+//     products, ONE rounding to T — the arithmetic of the production projector's epilogue, radon_internal.h epi_combine) with the fused
 //     sum of squares; the damped-LSQR update is the production template itself (gemv.hip, k_lsqr_damped_update<T, ..>).
 //   * trk_gk_lsqr_chain: the engine's arrangement of Hybrid-LSQR at a fixed lambda (krylov.GKState(normalized=False): U[j] =
 //     beta_j u_j, V[j] = alpha_j v_j, squared norms as device doubles, the divisions folded into the next step's coefficients;
@@ -159,7 +159,7 @@ __global__ __launch_bounds__(NT) void k_ref_radon_adj(const T* __restrict__ sino
 }
 
 // ---------------------------------------------------------------------------------------------- vector kernels on T
-// out = a x + b z: float64 coefficients and products, one rounding of the result (radon2d.hip epi_combine, on == 2), fused sum of
+// out = a x + b z: float64 coefficients and products, one rounding of the result (radon_internal.h epi_combine, on == 2), fused sum of
 // the squares of the ROUNDED outputs in float64.  x may alias out.
 template <class T>
 __global__ __launch_bounds__(NT) void k_ref_axpby(int64_t n, Coef ca, const T* x, Coef cb, const T* z, T* out, double* __restrict__ partials) {

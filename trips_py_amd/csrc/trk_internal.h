@@ -362,7 +362,7 @@ struct trk_op;
 struct PostReq;
 namespace trk {
 // ---- the float64 instrument (ref64.hip) ----
-// radon2d.hip: one angle of a parallel-beam handle in float64 (q(d, tt) = (d - (nd-1)/2) inv + k0 + tt dq, weight w = scale / |cos|
+// radon2d.hip (radon_create_impl): one angle of a parallel-beam handle in float64 (q(d, tt) = (d - (nd-1)/2) inv + k0 + tt dq, weight w = scale / |cos|
 // or / |sin|, mode 1 = marching columns) and the handle's sizes + fixed-point tables
 struct RadonRefAngle {
   double inv, dq, k0, w;
