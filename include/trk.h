@@ -306,7 +306,7 @@ int trk_arnoldi_step_post_dot(trk_op* op, float* V, int64_t ld, int k, float* w,
  * 2 (2 capacity + 4) doubles, all the caller's for the life of the handle: nothing in the Arnoldi process waits for a projected
  * solution, so consecutive iterates' O(k^3) jobs run side by side) and launches x_k = V_k y_k (trk_gemv_n_hosty) when the job is
  * collected, n_workers calls later.  create: the arguments of
- * trk_arnoldi_step with V[0] = b / ||b|| in place, beta0 = ||b||, at most `capacity` steps; start: enqueues step 1.  iter (projected.hip):
+ * trk_arnoldi_step with V[0] = b / ||b|| in place, beta0 = ||b||, at most `capacity` steps; start: enqueues step 1.  iter (hybrid_host.hip):
  * absorb (wait for the oldest posted step, install its column of H), enqueue_next, x_done != NULL (collect the OLDEST posted job:
  * *done_ii, its lambda, the reference's relResidual (:80); x_done launched, + ||x - ref||^2 block partials, *done_blocks of them, when
  * ref != NULL), post_job (iterate = columns - 1; needs a free worker).  H: a view of the columns installed so far, H[i + j * ldh],
