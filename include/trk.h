@@ -406,6 +406,11 @@ int trk_cgls_p_update_to(int64_t n, const float* t, const float* p, float* p_out
 int trk_cgls_xs_update(int64_t n, int count, int k_last, double* S, const double* gamma_new, int gamma_new_n, const float* x,
                        const float* p, const float* ring, int64_t ring_ld, int s_slots, int first, const float* t, float* x_new,
                        float* p_out, const float* x_true, double* NP, int capacity_blocks, int* n_blocks, trk_stream stream);
+/* trk_cgls_xs_update without the direction update: the x updates and norms alone (no t, no p_out, no gamma_new; delta_{k_last} and
+ * every gamma before it must be finished in S).  Same steps, same slices, same bits for x_new and the norms. */
+int trk_cgls_xs_update_x(int64_t n, int count, int k_last, const double* S, const float* x, const float* p, const float* ring,
+                         int64_t ring_ld, int s_slots, int first, float* x_new, const float* x_true, double* NP,
+                         int capacity_blocks, int* n_blocks, trk_stream stream);
 
 /* ---------------------------------------------------------------- fused CGLS fast path --- */
 /* For operators whose kernel can combine two inputs on load (the blur): one CGLS iteration becomes three launches with no
@@ -422,6 +427,23 @@ int trk_op_fused_caps(const trk_op* op, int* can_fuse);
 int trk_op_apply_fused(trk_op* op, int transpose, const float* x1, const float* x2, double sign, const double* num,
                        int num_n, const double* den, int den_n, float* comb_out, float* y, double* ysq_partials,
                        int capacity, int* n_partials, trk_stream stream);
+/* Recomputing instead of storing (the large-image CGLS loop trk_cgls_iterate_recompute): an operator's product applied twice, the first
+ * time for its norm alone, the second time consumed in the kernel's own store — the product itself never goes to memory.
+ *   trk_op_apply_sumsq_raw: sum(Op(x)^2) as *n_partials raw block partials, nothing else written — entry for entry the partials
+ *     trk_op_apply_fused with x2 = NULL leaves beside its output.
+ *   trk_op_apply_ratio: c = sign * (float)(S(num) / S(den)) (sign = +1 / -1; scalar sources, n >= 1; the ratio formed in double and
+ *     rounded once);  coef_on_z = 0: out = c Op(x) + z as fmaf(c, Op(x), z) — with sign = -1, num = gamma_old, den = the partials of
+ *     ||A p||^2 this is trk_cgls_r_update after an apply, to the bit;  coef_on_z = 1: out = Op(x) + c z as fmaf(c, z, Op(x)) —
+ *     trk_cgls_p_update_to after an apply, to the bit (one rounding, as that kernel is compiled).  out may be z (each entry is read and then written by the same thread); neither may
+ *     be x.  Workgroup 0 stores the finished S(den) (publish_den != 0) or S(num) to *publish (may be NULL).  All vectors 16-byte
+ *     aligned.
+ * trk_op_recompute_caps: *can = 1 when the operator has both (the separable blur up to 9x9 with ny % 4 == 0), else 0. */
+int trk_op_recompute_caps(const trk_op* op, int* can);
+int trk_op_apply_sumsq_raw(trk_op* op, int transpose, const float* x, double* ysq_partials, int capacity, int* n_partials,
+                           trk_stream stream);
+int trk_op_apply_ratio(trk_op* op, int transpose, const float* x, int coef_on_z, double sign, const double* num, int num_n,
+                       const double* den, int den_n, const float* z, float* out, double* publish, int publish_den,
+                       trk_stream stream);
 /* x_new = x + (S(gamma)/S(delta)) p (CGLS.py:64-65); block 0 stores the two finished scalars to publish_* (may be NULL);
  * [||x_new||^2, ||step*p||^2, ||x_new - x_true||^2] are left as *n_blocks x 3 raw partials (:76-80). */
 int trk_cgls_x_update(int64_t n, const double* gamma, int gamma_n, const double* delta, int delta_n, const float* x,
@@ -555,6 +577,21 @@ int trk_cgls_x_batch(int64_t n);
 int trk_cgls_iterate_xbatch(trk_op* A, int k_first, int n_iters, float* p, float* ring, int64_t ring_ld, int s, float* r, float* t,
                             float* w, float* X, int64_t x_ld, const float* x_prev, const float* x_true, double* S, double* NP,
                             int np_capacity_blocks, int* n_np_inout, double* PG, double* PD, int pcap, trk_stream stream);
+/* trk_cgls_iterate_xbatch with w = A p and t = A^T r recomputed instead of stored (operators with trk_op_recompute_caps), four launches
+ * and two reduction points per iteration as there:
+ *   F0  trk_op_apply_sumsq_raw(A, p_k) -> PD            F1  r <- r - (gamma_{k-1} / S(PD)) (A p_k) in place, publishes delta_k
+ *   [every s-th iteration and on the call's last one: trk_cgls_xs_update_x over the pending directions]
+ *   A0  trk_op_apply_sumsq_raw(A^T, r) -> PG            A1  p_{k+1} <- (A^T r) + (S(PG) / gamma_{k-1}) p_k, publishes gamma_k
+ * p_{k+1} goes to the next of the s slots, or — behind an x update, when the ring is free — over p_k (into p at the end of a call).
+ * 37n bytes per iteration at s = 8 instead of 44.5n.  Same arguments and the same state on return as trk_cgls_iterate_xbatch, bit
+ * for bit (x, p, r, S, NP, *n_np_inout), except that t and w are not touched (they may be NULL).  Only F1 / A1 take a slot of a
+ * kernel timer attached to the operator.
+ * trk_cgls_recompute: 1 where the loop is the faster one for vectors of n floats, 0 = off (measured rule; never on below
+ * trk_cgls_x_batch's threshold). */
+int trk_cgls_recompute(int64_t n);
+int trk_cgls_iterate_recompute(trk_op* A, int k_first, int n_iters, float* p, float* ring, int64_t ring_ld, int s, float* r, float* t,
+                               float* w, float* X, int64_t x_ld, const float* x_prev, const float* x_true, double* S, double* NP,
+                               int np_capacity_blocks, int* n_np_inout, double* PG, double* PD, int pcap, trk_stream stream);
 /* The same for operators with a fused apply (trk_op_fused_caps): three launches per iteration.  P, R: ping-pong pairs
  * [2][p_ld], [2][r_ld] (iteration k reads index (k-1) & 1, writes k & 1); PG / PD: gamma / delta block partials with
  * `pcap` doubles each; *n_g_inout: number of valid gamma partials in PG (set by the caller's r0/t0 setup). */

@@ -232,6 +232,16 @@ SIGNATURES = {
     "trk_cgls_iterate_xbatch": (c_int, [c_op, c_int, c_int, c_f32p, c_f32p, c_i64, c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_i64,
                                         c_f32p, c_f32p, c_f64p, c_f64p, c_int, ctypes.POINTER(c_int), c_f64p, c_f64p, c_int,
                                         c_stream]),
+    "trk_op_recompute_caps": (c_int, [c_op, ctypes.POINTER(c_int)]),
+    "trk_op_apply_sumsq_raw": (c_int, [c_op, c_int, c_f32p, c_f64p, c_int, ctypes.POINTER(c_int), c_stream]),
+    "trk_op_apply_ratio": (c_int, [c_op, c_int, c_f32p, c_int, c_dbl, c_f64p, c_int, c_f64p, c_int, c_f32p, c_f32p, c_f64p, c_int,
+                                   c_stream]),
+    "trk_cgls_xs_update_x": (c_int, [c_i64, c_int, c_int, c_f64p, c_f32p, c_f32p, c_f32p, c_i64, c_int, c_int, c_f32p, c_f32p,
+                                     c_f64p, c_int, ctypes.POINTER(c_int), c_stream]),
+    "trk_cgls_recompute": (c_int, [c_i64]),
+    "trk_cgls_iterate_recompute": (c_int, [c_op, c_int, c_int, c_f32p, c_f32p, c_i64, c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_i64,
+                                           c_f32p, c_f32p, c_f64p, c_f64p, c_int, ctypes.POINTER(c_int), c_f64p, c_f64p, c_int,
+                                           c_stream]),
     "trk_cgls_iterate_fused": (c_int, [c_op, c_int, c_int, c_f32p, c_i64, c_f32p, c_i64, c_f32p, c_f32p, c_f32p, c_i64, c_int,
                                        c_f32p, c_f32p, c_f64p, c_f64p, c_f64p, c_int, c_f64p, c_int, ctypes.POINTER(c_int),
                                        ctypes.POINTER(c_int), c_stream]),

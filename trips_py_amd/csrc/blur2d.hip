@@ -24,7 +24,7 @@
 // kernel (bmap<BC> below, valid at any distance from the image):
 //   reflect (half-sample symmetric, period 2n; the default)  constant (0)  nearest (clamp)  mirror (whole-sample, period
 //   2n-2)  wrap (period n).
-// Instantiated: every mode x every K of every kernel form — k_blur_slide plain / FUSE / EPI, k_blur_strip, k_blur_generic.
+// Instantiated: every mode x every K of every kernel form — k_blur_slide plain / FUSE / EPI / RC_NORM / RC_RATIO, k_blur_strip, k_blur_generic.
 // The reflect instantiations are the code that existed before the modes did (bmap<BC_REFLECT> == reflect()).  The "transpose"
 // is the flipped-PSF convolution in the same mode, as in the reference: the exact adjoint only for reflect / constant / wrap
 // with an odd symmetric PSF.
@@ -333,11 +333,37 @@ struct SlideEpi {
   Coef a, b;
 };
 
-template <int KH, int KW, int D, bool SUMSQ, bool FUSE, bool EPI = false, int BC = BC_REFLECT>
+// RC (the large-image CGLS loop that recomputes A p and A^T r instead of storing them, trk_cgls_iterate_recompute):
+//   RC_NORM   with SUMSQ: the output is NOT stored, only its sum of squares is taken — the same qacc / ss accumulation, the same
+//             block partials as the storing kernel, entry for entry.  8n bytes become 4n.
+//   RC_RATIO  with EPI: one coefficient of the pair is  c = sign * (float)(S(num) / S(den))  with scalar sources (a finished
+//             scalar or the block partials of an RC_NORM launch, added up by this wave as FUSE's cb is), the other is exactly 1:
+//             on_z = 0:  out = fmaf(c, A x, z)   (CGLS's r -= (gamma_old / S(delta)) (A p): fmaf(-step, w, r), k_cgls_r_update's bits)
+//             on_z = 1:  out = fmaf(c, z, A x)   (p' = (A^T r) + (S(gamma) / gamma_old) p: p_step4's bits — its fmaf(1.f, t, b * p) is
+//                        compiled as t + b * p contracted into ONE fma, a single rounding)
+//             and workgroup 0 publishes the finished S(den) (pub_den) or S(num) to *pub.  `out` MAY BE `z`: a lane reads z only at its
+//             own four columns of its own band's rows, each D outputs before it stores that very row — no other lane, of this wave
+//             or of another, touches those entries.  Both travel in this struct and not through the kernel's __restrict__ y.
+//             `out` / `z` must not alias x (neighbouring bands read each other's halo rows of x).
+enum Rc : int { RC_NONE = 0, RC_NORM = 1, RC_RATIO = 2 };
+struct SlideRatio {
+  const float* z;
+  float* out;
+  ScalarSrc num, den;
+  float sign;
+  int on_z, pub_den;
+  double* pub;         // may be NULL
+};
+
+template <int KH, int KW, int D, bool SUMSQ, bool FUSE, bool EPI = false, int BC = BC_REFLECT, int RC = RC_NONE>
 __global__ __launch_bounds__(64) void k_blur_slide(const float* __restrict__ x, int64_t ldx, float* __restrict__ y,
                                                    int64_t ldy, int nx, int ny, const float* __restrict__ wts,
                                                    double* __restrict__ partials, int spans_x, int nbands,
-                                                   int rows_per_band, SlideFuse fz, int nt_store, SlideEpi ep = SlideEpi{}) {
+                                                   int rows_per_band, SlideFuse fz, int nt_store, SlideEpi ep = SlideEpi{},
+                                                   SlideRatio rq = SlideRatio{}) {
+  static_assert(RC == RC_NONE || !FUSE, "the recompute forms take one operand");
+  static_assert(RC != RC_NORM || (SUMSQ && !EPI), "RC_NORM: the sum of squares alone");
+  static_assert(RC != RC_RATIO || (EPI && !SUMSQ), "RC_RATIO: an epilogue form without a sum");
   constexpr int T = KH - 1 - KH / 2;
   constexpr int Lh = KW - 1 - KW / 2;
   constexpr int OFFC = 4 - Lh;          // v[] index of tap 0 of output column 0
@@ -373,7 +399,7 @@ __global__ __launch_bounds__(64) void k_blur_slide(const float* __restrict__ x, 
 
   const unsigned img_bytes = (unsigned)nx * (unsigned)ny * 4u;
   const auto rin = __builtin_amdgcn_make_buffer_rsrc((void*)x, 0, img_bytes, 0x00020000);
-  const auto rout = __builtin_amdgcn_make_buffer_rsrc((void*)y, 0, img_bytes, 0x00020000);
+  const auto rout = __builtin_amdgcn_make_buffer_rsrc((void*)(RC == RC_RATIO ? rq.out : y), 0, img_bytes, 0x00020000);
   const auto rin2 = __builtin_amdgcn_make_buffer_rsrc((void*)(FUSE ? fz.x2 : x), 0, img_bytes, 0x00020000);
   const auto rcomb = __builtin_amdgcn_make_buffer_rsrc((void*)(FUSE ? fz.comb : y), 0, img_bytes, 0x00020000);
   float cb = 0.f;
@@ -434,13 +460,22 @@ __global__ __launch_bounds__(64) void k_blur_slide(const float* __restrict__ x, 
   // EPI: coefficients (device scalars, wave-uniform) and the ring of z rows, output o in slot o % D
   float ea = 1.f, eb = 0.f;
   f4 zq[EPI ? D : 1];
-  const auto rz = __builtin_amdgcn_make_buffer_rsrc((void*)((EPI && ep.z) ? ep.z : x), 0, img_bytes, 0x00020000);
-  const bool has_z = EPI && ep.z != nullptr;
+  const auto rz = __builtin_amdgcn_make_buffer_rsrc((void*)(RC == RC_RATIO ? rq.z : (EPI && ep.z) ? ep.z : x), 0, img_bytes, 0x00020000);
+  const bool has_z = RC == RC_RATIO || (EPI && ep.z != nullptr);
   auto issue_z = [&](int o, int slot) {
     const int oc = o < band_rows - 1 ? o : band_rows - 1;                 // (beyond the band: any valid row, never used)
     zq[slot] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(rz, vc, (ofirst + dir * oc) * rowbytes, 0));
   };
-  if (EPI) {
+  if constexpr (RC == RC_RATIO) {
+#pragma unroll
+    for (int d = 0; d < D; ++d) issue_z(d, d);
+    // the first D rows of the operand and of z are on their way: the partials are added up behind them
+    const double qn = scalar_from_wave(rq.num, lane), qd = scalar_from_wave(rq.den, lane);
+    const float c = rq.sign * (float)(qn / qd);          // the ratio in double, rounded once
+    ea = rq.on_z ? 1.f : c;
+    eb = rq.on_z ? c : 1.f;
+    if (blockIdx.x == 0 && blockIdx.y == 0 && lane == 0 && rq.pub) *rq.pub = rq.pub_den ? qd : qn;
+  } else if (EPI) {
     ea = (float)coef_eval(ep.a);
     eb = has_z ? (float)coef_eval(ep.b) : 0.f;
     if (has_z) {
@@ -523,7 +558,17 @@ __global__ __launch_bounds__(64) void k_blur_slide(const float* __restrict__ x, 
         f4 out = (f4){acc[kd][0][0], acc[kd][0][1], acc[kd][1][0], acc[kd][1][1]};
         if (EPI) {
           const int zs = pmod(u - (KH - 1), D);                             // = o % D: U is a multiple of D
-          if (has_z) {                                                       // grid-uniform
+          if constexpr (RC == RC_RATIO) {
+            const f4 zv = zq[zs];
+            if (rq.on_z) {                                                   // grid-uniform
+#pragma unroll
+              for (int e = 0; e < 4; ++e) out[e] = fmaf(eb, zv[e], out[e]);
+            } else {
+#pragma unroll
+              for (int e = 0; e < 4; ++e) out[e] = fmaf(ea, out[e], zv[e]);
+            }
+            issue_z(o + D, zs);
+          } else if (has_z) {                                                // grid-uniform
             const f4 zv = zq[zs];
 #pragma unroll
             for (int e = 0; e < 4; ++e) out[e] = fmaf(ea, out[e], eb * zv[e]);
@@ -539,10 +584,12 @@ __global__ __launch_bounds__(64) void k_blur_slide(const float* __restrict__ x, 
         if (active) {
           // aux = 2: non-temporal store, for images too large for the next kernel to find the output cached
           // (stream_nontemporal(); 4096^2: 23.9 -> 23.2 us in the CGLS loop); nt_store is grid-uniform
-          if (nt_store & 1)
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, out), rout, vst + (ofirst + dir * o) * rowbytes, 0, 2);
-          else
-            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, out), rout, vst + (ofirst + dir * o) * rowbytes, 0, 0);
+          if constexpr (RC != RC_NORM) {
+            if (nt_store & 1)
+              __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, out), rout, vst + (ofirst + dir * o) * rowbytes, 0, 2);
+            else
+              __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, out), rout, vst + (ofirst + dir * o) * rowbytes, 0, 0);
+          }
           if (SUMSQ) qacc = fmaf(out[0], out[0], fmaf(out[1], out[1], fmaf(out[2], out[2], fmaf(out[3], out[3], qacc))));
         }
       }
@@ -630,25 +677,25 @@ int launch_slide(const BlurImpl* im, int tr, const float* x, int64_t ldx, float*
   const float* w = im->sep_dev[tr];
   const int nts = stream_nontemporal((int64_t)im->nx * im->ny);
   if (fuse) {   // fused-operand form: always with the sum of squares (raw partials)
-    hipExtLaunchKernelGGL((k_blur_slide<K, K, D, true, true, false, BC>), grid, block, 0, s, ev0, ev1, 0, x, ldx, y, ldy, im->nx, im->ny, w, part, spans_x, nbands, rows_per_band, *fuse, nts, SlideEpi{});
+    hipExtLaunchKernelGGL((k_blur_slide<K, K, D, true, true, false, BC>), grid, block, 0, s, ev0, ev1, 0, x, ldx, y, ldy, im->nx, im->ny, w, part, spans_x, nbands, rows_per_band, *fuse, nts, SlideEpi{}, SlideRatio{});
     TRK_LAUNCH_CHECK();
     return TRK_OK;
   }
   const SlideFuse nofuse{nullptr, nullptr, 0.0, {nullptr, 0}, {nullptr, 0}};
   if (epi) {
     if (part)
-      hipExtLaunchKernelGGL((k_blur_slide<K, K, D, true, false, true, BC>), grid, block, 0, s, ev0, ev1, 0, x, ldx, y, ldy, im->nx, im->ny, w, part, spans_x, nbands, rows_per_band, nofuse, nts, *epi);
+      hipExtLaunchKernelGGL((k_blur_slide<K, K, D, true, false, true, BC>), grid, block, 0, s, ev0, ev1, 0, x, ldx, y, ldy, im->nx, im->ny, w, part, spans_x, nbands, rows_per_band, nofuse, nts, *epi, SlideRatio{});
     else
-      hipExtLaunchKernelGGL((k_blur_slide<K, K, D, false, false, true, BC>), grid, block, 0, s, ev0, ev1, 0, x, ldx, y, ldy, im->nx, im->ny, w, part, spans_x, nbands, rows_per_band, nofuse, nts, *epi);
+      hipExtLaunchKernelGGL((k_blur_slide<K, K, D, false, false, true, BC>), grid, block, 0, s, ev0, ev1, 0, x, ldx, y, ldy, im->nx, im->ny, w, part, spans_x, nbands, rows_per_band, nofuse, nts, *epi, SlideRatio{});
     TRK_LAUNCH_CHECK();
     return TRK_OK;
   }
   // hipExtLaunchKernelGGL attaches the (optional) events to the dispatch itself: their timestamps are the kernel's own
   // begin / end, the same quantity rocprofv3's kernel trace reports.
   if (part)
-    hipExtLaunchKernelGGL((k_blur_slide<K, K, D, true, false, false, BC>), grid, block, 0, s, ev0, ev1, 0, x, ldx, y, ldy, im->nx, im->ny, w, part, spans_x, nbands, rows_per_band, nofuse, nts, SlideEpi{});
+    hipExtLaunchKernelGGL((k_blur_slide<K, K, D, true, false, false, BC>), grid, block, 0, s, ev0, ev1, 0, x, ldx, y, ldy, im->nx, im->ny, w, part, spans_x, nbands, rows_per_band, nofuse, nts, SlideEpi{}, SlideRatio{});
   else
-    hipExtLaunchKernelGGL((k_blur_slide<K, K, D, false, false, false, BC>), grid, block, 0, s, ev0, ev1, 0, x, ldx, y, ldy, im->nx, im->ny, w, part, spans_x, nbands, rows_per_band, nofuse, nts, SlideEpi{});
+    hipExtLaunchKernelGGL((k_blur_slide<K, K, D, false, false, false, BC>), grid, block, 0, s, ev0, ev1, 0, x, ldx, y, ldy, im->nx, im->ny, w, part, spans_x, nbands, rows_per_band, nofuse, nts, SlideEpi{}, SlideRatio{});
   TRK_LAUNCH_CHECK();
   return TRK_OK;
 }
@@ -846,6 +893,65 @@ int blur_apply_axpby_plain(trk_op* op, int tr, const float* x, Coef a, Coef b, c
   return TRK_OK;
 }
 
+// The two launches the recomputing CGLS loop makes of each product (trk_op_apply_sumsq_raw, trk_op_apply_ratio): the sum of squares
+// of Op(x) alone, as the block partials blur_apply_fused would leave beside its output (same grid, same order, same bits), and
+// out = c Op(x) + z  /  Op(x) + c z  with c from scalar sources (k_blur_slide's RC_NORM / RC_RATIO).  Only the second takes a timer slot.
+template <int K, int D, int BC>
+int launch_slide_rc(const BlurImpl* im, int tr, const float* x, double* part, const SlideRatio* rq, int spans_x, int nbands,
+                    int rows_per_band, hipStream_t s, hipEvent_t ev0, hipEvent_t ev1) {
+  dim3 grid(spans_x * nbands, 1), block(64);
+  const float* w = im->sep_dev[tr];
+  const SlideFuse nofuse{nullptr, nullptr, 0.0, {nullptr, 0}, {nullptr, 0}};
+  if (rq)   // plain stores (nt_store = 0): the output is read again by the two launches that follow; stored non-temporally as the plain
+            // blur's output is from 11 M unknowns, the loop at 4096^2 ran at 8.43 k iterations/s instead of 8.85 k
+    hipExtLaunchKernelGGL((k_blur_slide<K, K, D, false, false, true, BC, RC_RATIO>), grid, block, 0, s, ev0, ev1, 0, x, 0, rq->out, 0, im->nx, im->ny, w, part, spans_x, nbands, rows_per_band, nofuse, 0, SlideEpi{}, *rq);
+  else
+    hipExtLaunchKernelGGL((k_blur_slide<K, K, D, true, false, false, BC, RC_NORM>), grid, block, 0, s, ev0, ev1, 0, x, 0, (float*)nullptr, 0, im->nx, im->ny, w, part, spans_x, nbands, rows_per_band, nofuse, 0, SlideEpi{}, SlideRatio{});
+  TRK_LAUNCH_CHECK();
+  return TRK_OK;
+}
+
+int blur_apply_rc(trk_op* op, int tr, const float* x, double* partials, int cap, int* n_partials, const SlideRatio* rq, hipStream_t s) {
+  auto* im = static_cast<BlurImpl*>(op->impl);
+  if (!slide_shape_ok(im) || !aligned16(x) || (rq && (!aligned16(rq->z) || !aligned16(rq->out))))
+    return fail(TRK_EUNSUPPORTED, "blur2d recompute forms: need a separable odd PSF <= 9x9, ny %% 4 == 0, 16-byte aligned buffers");
+  if (rq && (rq->out == x || rq->z == x))
+    return fail(TRK_EINVAL, "blur2d ratio apply: out / z must not alias x (halo rows are shared)");
+  int spans_x, nbands, rpb;
+  const int Usel = (im->kh == 9) ? 9 : (im->kh == 7) ? 7 : (im->kh == 5) ? 5 : 6;      // lcm(KH, D) of the instantiations below
+  slide_grid(im->nx, im->ny, 1, im->kh, Usel, &spans_x, &nbands, &rpb);
+  if (!rq) {
+    const int nblk = spans_x * nbands;
+    if (nblk > cap) return fail(TRK_EINVAL, "blur2d norm-only apply: partial buffer holds %d doubles, %d needed", cap, nblk);
+    *n_partials = nblk;
+  }
+  hipEvent_t ev0 = nullptr, ev1 = nullptr;
+  if (trk_timer* t = op->timer)
+    if (rq && (op->timer_which == 2 || op->timer_which == tr) && t->used < t->cap) {
+      ev0 = t->ev[2 * t->used];
+      ev1 = t->ev[2 * t->used + 1];
+      ++t->used;
+    }
+  return bc_dispatch(im->bc, [&](auto bc) {
+    constexpr int BC = decltype(bc)::value;
+    switch (im->kh) {
+      case 3: return launch_slide_rc<3, 6, BC>(im, tr, x, partials, rq, spans_x, nbands, rpb, s, ev0, ev1);
+      case 5: return launch_slide_rc<5, 5, BC>(im, tr, x, partials, rq, spans_x, nbands, rpb, s, ev0, ev1);
+      case 7: return launch_slide_rc<7, 7, BC>(im, tr, x, partials, rq, spans_x, nbands, rpb, s, ev0, ev1);
+      default: return launch_slide_rc<9, 9, BC>(im, tr, x, partials, rq, spans_x, nbands, rpb, s, ev0, ev1);
+    }
+  });
+}
+
+int blur_apply_norm(trk_op* op, int tr, const float* x, double* partials, int cap, int* n_partials, hipStream_t s) {
+  return blur_apply_rc(op, tr, x, partials, cap, n_partials, nullptr, s);
+}
+
+int blur_apply_ratio(trk_op* op, int tr, const float* x, const RatioCoef& c, const float* z, float* out, hipStream_t s) {
+  const SlideRatio rq{z, out, c.num, c.den, (float)c.sign, c.on_z, c.pub_den, c.pub};
+  return blur_apply_rc(op, tr, x, nullptr, 0, nullptr, &rq, s);
+}
+
 void blur_destroy(trk_op* op) {
   auto* im = static_cast<BlurImpl*>(op->impl);
   for (int t = 0; t < 2; ++t) {
@@ -953,6 +1059,10 @@ extern "C" int trk_blur2d_create_bc(const double* psf, int kh, int kw, int nx, i
   auto* op = new trk_op{1, n, n, im, blur_apply, blur_destroy, nullptr, 0};
   if (slide_shape_ok(im)) op->apply_fused = blur_apply_fused;
   if (slide_shape_ok(im)) op->apply_axpby_plain = blur_apply_axpby_plain;
+  if (slide_shape_ok(im)) {
+    op->apply_norm = blur_apply_norm;
+    op->apply_ratio = blur_apply_ratio;
+  }
   *out = op;
   return TRK_OK;
 }

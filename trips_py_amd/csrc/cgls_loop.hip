@@ -144,6 +144,69 @@ int trk_cgls_iterate_xbatch(trk_op* A, int k_first, int n_iters, float* p, float
   return TRK_OK;
 }
 
+// Where the recomputing loop below replaces trk_cgls_iterate_xbatch (1 = on).  Measured (iterations/s at s = 8, x-batch loop vs recompute,
+// median of three, spread of the runs below 0.4 % everywhere; profiles/recompute/sweep.txt):
+//   3072^2 12.74 k vs 13.11 k (+2.9 %) | 3584^2 9.87 k vs 10.27 k (+4.0 %) | 4096^2 8.14 k vs 8.85 k (+8.7 %) | 4608^2 6.44 k vs 6.82 k (+5.9 %) |
+//   5120^2 5.23 k vs 5.60 k (+7.1 %) | 6144^2 3.12 k vs 3.92 k (+25.8 %) | 8192^2 1.77 k vs 2.01 k (+13.9 %)
+// faster at every size the x-batch loop is used at, so the threshold is that loop's (trk_cgls_x_batch); nothing was measured below it.
+int trk_cgls_recompute(int64_t n) {
+  return n >= ((int64_t)8 << 20) ? 1 : 0;
+}
+
+// trk_cgls_iterate_xbatch without the two temporaries: w = A p_k and t = A^T r are never stored.  Each product is applied twice — once
+// for its norm alone (the reduction that must be finished before the coefficient exists), once with the update it feeds as the kernel's
+// own epilogue: r <- r - alpha (A p_k) in place, p_{k+1} <- (A^T r) + beta p_k.  Same launch count, same S / NP / PG / PD layout and slot
+// arithmetic, the same fp32 operations on every entry (k_blur_slide RC_RATIO), 37n bytes per iteration at s = 8 instead of 44.5n.
+// The x update cannot ride on the p update any more (there is no t to read): it is made alone (trk_cgls_xs_update_x) between F1, which
+// publishes the delta_k its last step needs, and A0 — before A1 writes a new direction, so that the ring is free by then and p_{k+1}
+// may go over p_k.
+int trk_cgls_iterate_recompute(trk_op* A, int k_first, int n_iters, float* p, float* ring, int64_t ring_ld, int s, float* r, float* t,
+                               float* w, float* X, int64_t x_ld, const float* x_prev, const float* x_true, double* S, double* NP,
+                               int np_capacity_blocks, int* n_np_inout, double* PG, double* PD, int pcap, trk_stream stream) {
+  (void)t;
+  (void)w;
+  TRK_REQUIRE(A && p && r && X && x_prev && S && NP && n_np_inout && PG && PD && pcap > 0, "trk_cgls_iterate_recompute: NULL argument");
+  TRK_REQUIRE(A->apply_norm && A->apply_ratio, "trk_cgls_iterate_recompute: the operator has no recompute forms (trk_op_recompute_caps)");
+  TRK_REQUIRE(A->rows == A->cols, "trk_cgls_iterate_recompute: square operators only");
+  TRK_REQUIRE(k_first >= 1 && n_iters >= 0, "trk_cgls_iterate_recompute: need k_first >= 1, n_iters >= 0");
+  TRK_REQUIRE(s >= 1 && (s == 1 || (ring && ring_ld >= A->cols)), "trk_cgls_iterate_recompute: s > 1 needs a ring of s - 1 directions");
+  const int64_t n = A->cols;
+  int n_np = *n_np_inout;
+  auto slot = [&](int j) { return j == 0 ? p : ring + (int64_t)(j - 1) * ring_ld; };   // as trk_cgls_iterate_xbatch
+  int cur = 0, pending = 0;
+  const int k_end = k_first + n_iters;
+  for (int k = k_first; k < k_end; ++k) {
+    double* row = S + 5 * (int64_t)k;                     // [delta, gamma, ||x||^2, ||dx||^2, ||x-xt||^2]
+    const double* gamma_old = (k == 1) ? S : row - 4;
+    float* p_k = slot(cur);
+    int n_d = 0, n_g = 0;
+    int rc = trk_op_apply_sumsq_raw(A, 0, p_k, PD, pcap, &n_d, stream);                                        // F0
+    if (rc) return rc;
+    rc = trk_op_apply_ratio(A, 0, p_k, 0, -1.0, gamma_old, 1, PD, n_d, r, r, row, 1, stream);                   // F1
+    if (rc) return rc;
+    const bool last = k + 1 == k_end;
+    const bool batch = ++pending >= s || last;
+    if (batch) {                                          // x_{k-pending+1} .. x_k in one pass, x_k where trk_cgls_iterate writes it
+      float* x_new = X + (int64_t)((k - 1) & 1) * x_ld;
+      rc = trk_cgls_xs_update_x(n, pending, k, S, x_prev, p, ring, ring_ld, s, (cur - pending + 1 + s) % s, x_new, x_true, NP,
+                                np_capacity_blocks, &n_np, stream);
+      if (rc) return rc;
+      x_prev = x_new;
+      pending = 0;
+    }
+    rc = trk_op_apply_sumsq_raw(A, 1, r, PG, pcap, &n_g, stream);                                              // A0
+    if (rc) return rc;
+    // p_{k+1}: behind an x update over p_k (it stays cached for F0), at the end of the call into the caller's p; else the next slot
+    float* p_next = batch ? (last ? p : p_k) : slot((cur + 1) % s);
+    rc = trk_op_apply_ratio(A, 1, r, 1, 1.0, PG, n_g, gamma_old, 1, p_k, p_next, row + 1, 0, stream);           // A1
+    if (rc) return rc;
+    if (!batch) cur = (cur + 1) % s;
+    if (last) cur = 0;
+  }
+  *n_np_inout = n_np;
+  return TRK_OK;
+}
+
 int trk_cgls_iterate_fused(trk_op* A, int k_first, int n_iters, float* P, int64_t p_ld, float* R, int64_t r_ld, float* t,
                            float* w, float* X, int64_t x_ld, int keep_history, const float* x_prev, const float* x_true,
                            double* S, double* PG, double* PD, int pcap, double* NP, int np_capacity_blocks,

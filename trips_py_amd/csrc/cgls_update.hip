@@ -254,7 +254,9 @@ struct XsDirs {
   const float* p[XS_MAX];                 // p_{k-C+1} .. p_k
 };
 
-template <bool HAS_XT, int C>
+// XONLY (trk_cgls_xs_update_x, the recomputing loop): the x updates and their norms alone — no t is loaded, no p_out stored, no gamma_new
+// summed or published; the last direction is read again soon (the adjoint's epilogue) and is loaded plainly.
+template <bool HAS_XT, int C, bool XONLY = false>
 __global__ __launch_bounds__(NT) void k_cgls_xs_update(int64_t n, const double* S, int k, ScalarSrc gnew, const float* x, XsDirs dirs,
                                                        const float* __restrict__ t, float* x_new, float* p_out,
                                                        const float* __restrict__ x_true, double* pub_gamma,
@@ -262,7 +264,7 @@ __global__ __launch_bounds__(NT) void k_cgls_xs_update(int64_t n, const double* 
   __shared__ double lds[NT / 64];
   __shared__ double bc[C + 1];
   if (threadIdx.x < 64) {
-    const double g = scalar_from_wave(gnew, threadIdx.x);
+    const double g = XONLY ? 0.0 : scalar_from_wave(gnew, threadIdx.x);
     if (threadIdx.x == 0) {
 #pragma unroll
       for (int c = 0; c < C; ++c) {
@@ -270,15 +272,17 @@ __global__ __launch_bounds__(NT) void k_cgls_xs_update(int64_t n, const double* 
         const double* gold = (j == 1) ? S : S + 5 * (int64_t)(j - 1) + 1;
         bc[c] = *gold / S[5 * (int64_t)j];
       }
-      bc[C] = g / *((k == 1) ? S : S + 5 * (int64_t)(k - 1) + 1);
-      if (blockIdx.x == 0 && pub_gamma) *pub_gamma = g;
+      if (!XONLY) {
+        bc[C] = g / *((k == 1) ? S : S + 5 * (int64_t)(k - 1) + 1);
+        if (blockIdx.x == 0 && pub_gamma) *pub_gamma = g;
+      }
     }
   }
   __syncthreads();
   float step[C];
 #pragma unroll
   for (int c = 0; c < C; ++c) step[c] = (float)bc[c];
-  const float b = (float)bc[C];
+  const float b = XONLY ? 0.f : (float)bc[C];
   double s0[C], s1[C], s2[C];
 #pragma unroll
   for (int c = 0; c < C; ++c) s0[c] = s1[c] = s2[c] = 0.0;
@@ -289,7 +293,8 @@ __global__ __launch_bounds__(NT) void k_cgls_xs_update(int64_t n, const double* 
     float4 pv[C];
 #pragma unroll
     for (int c = 0; c < C; ++c) pv[c] = (nt & (c < C - 1 ? 256 : 512)) ? ld4_nt(dirs.p[c], i) : ld4(dirs.p[c], i);
-    const float4 tv = (nt & 32) ? ld4_nt(t, i) : ld4(t, i);
+    float4 tv = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (!XONLY) tv = (nt & 32) ? ld4_nt(t, i) : ld4(t, i);
     const float4 tt = HAS_XT ? ld4(x_true, i) : make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
     for (int c = 0; c < C; ++c) {
@@ -298,14 +303,16 @@ __global__ __launch_bounds__(NT) void k_cgls_xs_update(int64_t n, const double* 
       x_norms4<HAS_XT>(xv, d, tt, s0[c], s1[c], s2[c]);
     }
     if (nt & 2) st4_nt(x_new, i, xv); else st4(x_new, i, xv);
-    if (nt & 1024) st4_nt(p_out, i, p_step4(tv, pv[C - 1], b)); else st4(p_out, i, p_step4(tv, pv[C - 1], b));
+    if (!XONLY) {
+      if (nt & 1024) st4_nt(p_out, i, p_step4(tv, pv[C - 1], b)); else st4(p_out, i, p_step4(tv, pv[C - 1], b));
+    }
   }
   for (int64_t i = (n4 << 2) + tid; i < n; i += nth) {
     float xv = x[i];
     float pv[C];
 #pragma unroll
     for (int c = 0; c < C; ++c) pv[c] = dirs.p[c][i];
-    const float tv = t[i], tt = HAS_XT ? x_true[i] : 0.f;
+    const float tv = XONLY ? 0.f : t[i], tt = HAS_XT ? x_true[i] : 0.f;
 #pragma unroll
     for (int c = 0; c < C; ++c) {
       float d;
@@ -313,7 +320,7 @@ __global__ __launch_bounds__(NT) void k_cgls_xs_update(int64_t n, const double* 
       x_norms<HAS_XT>(xv, d, tt, s0[c], s1[c], s2[c]);
     }
     x_new[i] = xv;
-    p_out[i] = fmaf(1.f, tv, b * pv[C - 1]);
+    if (!XONLY) p_out[i] = fmaf(1.f, tv, b * pv[C - 1]);
   }
 #pragma unroll
   for (int c = 0; c < C; ++c) {
@@ -395,6 +402,14 @@ void launch_xs(int count, bool has_xt, int grid, hipStream_t s, Args... args) {
     with_bools([&](auto HAS_XT) { hipLaunchKernelGGL((k_cgls_xs_update<HAS_XT, C>), dim3(grid), dim3(NT), 0, s, args...); }, has_xt);
   } else if constexpr (C > 1) {
     launch_xs<C - 1>(count, has_xt, grid, s, args...);
+  }
+}
+template <int C = XS_MAX, class... Args>
+void launch_xs_x(int count, bool has_xt, int grid, hipStream_t s, Args... args) {
+  if (count == C) {
+    with_bools([&](auto HAS_XT) { hipLaunchKernelGGL((k_cgls_xs_update<HAS_XT, C, true>), dim3(grid), dim3(NT), 0, s, args...); }, has_xt);
+  } else if constexpr (C > 1) {
+    launch_xs_x<C - 1>(count, has_xt, grid, s, args...);
   }
 }
 
@@ -528,6 +543,35 @@ int trk_cgls_xs_update(int64_t n, int count, int k_last, double* S, const double
   double* pub = S + 5 * (int64_t)k_last + 1;
   const int nt = stream_nontemporal(n) | (count > 1 ? kXsOldDirs | (p_out == dirs.p[count - 1] ? 0 : kXsLastDirAndOut) : 0);
   launch_xs(count, x_true != nullptr, grid, s, n, (const double*)S, k_last, g, x, dirs, t, x_new, p_out, x_true, pub, part, slice, nt);
+  TRK_LAUNCH_CHECK();
+  return TRK_OK;
+}
+
+int trk_cgls_xs_update_x(int64_t n, int count, int k_last, const double* S, const float* x, const float* p, const float* ring,
+                         int64_t ring_ld, int s_slots, int first, float* x_new, const float* x_true, double* NP,
+                         int capacity_blocks, int* n_blocks, trk_stream st) {
+  TRK_REQUIRE(S && x && p && x_new && NP && n_blocks && n >= 0, "trk_cgls_xs_update_x: bad argument");
+  TRK_REQUIRE(count >= 1 && count <= XS_MAX && count <= k_last, "trk_cgls_xs_update_x: need 1 <= count <= %d and count <= k_last", XS_MAX);
+  TRK_REQUIRE(s_slots >= count && first >= 0 && first < s_slots && (s_slots == 1 || (ring && ring_ld >= n)),
+              "trk_cgls_xs_update_x: need count <= s_slots, 0 <= first < s_slots and a ring of s_slots - 1 directions");
+  XsDirs dirs{};
+  for (int c = 0; c < count; ++c) {
+    const int slot = (first + c) % s_slots;                  // slot 0 is p, slot j the ring's row j - 1
+    dirs.p[c] = slot == 0 ? p : ring + (int64_t)(slot - 1) * ring_ld;
+  }
+  bool al = aligned16(x) && aligned16(x_new) && (!x_true || aligned16(x_true));
+  for (int c = 0; c < count; ++c) al = al && aligned16(dirs.p[c]);
+  TRK_REQUIRE(al, "trk_cgls_xs_update_x: vectors must be 16-byte aligned");
+  const int grid = stream_grid(n);
+  TRK_REQUIRE(grid <= capacity_blocks, "trk_cgls_xs_update_x: partial buffer too small (%d blocks needed)", grid);
+  *n_blocks = grid;
+  hipStream_t s = (hipStream_t)st;
+  const int64_t slice = 3 * (int64_t)grid;
+  double* part = NP + slice * (k_last - count);              // iteration j's slice: NP + 3 * grid * (j - 1)
+  // the directions before the last are read here for the last time; the last one is the z of the adjoint's epilogue two launches on
+  const int nt = (stream_nontemporal(n) & ~32) | (count > 1 ? 256 : 0);
+  launch_xs_x(count, x_true != nullptr, grid, s, n, S, k_last, ScalarSrc{nullptr, 0}, x, dirs, (const float*)nullptr, x_new,
+              (float*)nullptr, x_true, (double*)nullptr, part, slice, nt);
   TRK_LAUNCH_CHECK();
   return TRK_OK;
 }

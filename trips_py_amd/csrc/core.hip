@@ -288,6 +288,30 @@ int trk_op_apply_fused(trk_op* op, int transpose, const float* x1, const float* 
                          ysq_partials, capacity, n_partials, (hipStream_t)stream);
 }
 
+int trk_op_recompute_caps(const trk_op* op, int* can) {
+  TRK_REQUIRE(op && can, "trk_op_recompute_caps: NULL argument");
+  *can = (op->apply_norm && op->apply_ratio) ? 1 : 0;
+  return TRK_OK;
+}
+
+int trk_op_apply_sumsq_raw(trk_op* op, int transpose, const float* x, double* ysq_partials, int capacity, int* n_partials,
+                           trk_stream stream) {
+  TRK_REQUIRE(op && x && ysq_partials && n_partials && capacity > 0, "trk_op_apply_sumsq_raw: bad argument");
+  if (!op->apply_norm) return fail(TRK_EUNSUPPORTED, "trk_op_apply_sumsq_raw: this operator has no norm-only form (trk_op_recompute_caps)");
+  return op->apply_norm(op, transpose ? 1 : 0, x, ysq_partials, capacity, n_partials, (hipStream_t)stream);
+}
+
+int trk_op_apply_ratio(trk_op* op, int transpose, const float* x, int coef_on_z, double sign, const double* num, int num_n,
+                       const double* den, int den_n, const float* z, float* out, double* publish, int publish_den,
+                       trk_stream stream) {
+  TRK_REQUIRE(op && x && z && out && num && den && num_n >= 1 && den_n >= 1, "trk_op_apply_ratio: bad argument");
+  TRK_REQUIRE(sign == 1.0 || sign == -1.0, "trk_op_apply_ratio: sign must be +1 or -1");
+  TRK_REQUIRE(out != x && z != x, "trk_op_apply_ratio: out / z must not alias x");
+  if (!op->apply_ratio) return fail(TRK_EUNSUPPORTED, "trk_op_apply_ratio: this operator has no ratio form (trk_op_recompute_caps)");
+  const RatioCoef c{ScalarSrc{num, num_n}, ScalarSrc{den, den_n}, sign, coef_on_z ? 1 : 0, publish_den ? 1 : 0, publish};
+  return op->apply_ratio(op, transpose ? 1 : 0, x, c, z, out, (hipStream_t)stream);
+}
+
 int trk_finalize_batched(const double* partials, int nblocks, int nvals, int batches, double* out, int out_stride,
                          trk_stream stream) {
   TRK_REQUIRE(partials && out && nblocks >= 1 && nvals >= 1 && batches >= 0, "trk_finalize_batched: bad argument");

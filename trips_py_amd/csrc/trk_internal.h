@@ -297,6 +297,15 @@ __device__ __forceinline__ double scalar_from_wave(const ScalarSrc s, int lane) 
   return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
 }
 
+// the coefficient of trk_op_apply_ratio: c = sign * (float)(S(num) / S(den)); on_z = 0: out = c Op(x) + z, 1: out = Op(x) + c z;
+// workgroup 0 stores the finished S(den) (pub_den != 0) or S(num) to *pub (may be NULL)
+struct RatioCoef {
+  ScalarSrc num, den;
+  double sign;
+  int on_z, pub_den;
+  double* pub;
+};
+
 inline int ceil_div(int64_t a, int64_t b) { return (int)((a + b - 1) / b); }
 
 // Cache hints for the streamed vectors of the large-image CGLS loop, as a mask: stores — bit 0 the blur kernel's output,
@@ -460,6 +469,11 @@ struct trk_op {
   // shapes / alignments its kernel does not take — the caller then falls back.
   int (*apply_axpby_plain)(trk_op*, int transpose, const float* x, trk::Coef a, trk::Coef b, const float* z, float* out,
                            double* sumsq, hipStream_t s) = nullptr;
+  // optional, as a pair (trk_op_recompute_caps): ||Op(x)||^2 alone as raw block partials, nothing stored (the partials of apply_fused
+  // with x2 = NULL, bit for bit), and out = c Op(x) + z / Op(x) + c z with c from scalar sources (out may be z; neither may be x)
+  int (*apply_norm)(trk_op*, int transpose, const float* x, double* partials, int cap, int* n_partials, hipStream_t s) = nullptr;
+  int (*apply_ratio)(trk_op*, int transpose, const float* x, const trk::RatioCoef& c, const float* z, float* out,
+                     hipStream_t s) = nullptr;
   // optional: finish what a TRK_HINT_SUMSQ_DEFERRED apply left unfinished (trk_op_flush)
   int (*flush)(trk_op*, hipStream_t s) = nullptr;
   // set for the duration of one trk_gk_step_proj call: the forward half step's output pass also leaves the block partials of

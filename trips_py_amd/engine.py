@@ -565,6 +565,42 @@ class HipEngine:
         _lib.check(rc, "trk_cgls_iterate_xbatch")
         return c.value
 
+    # ------------------------------------------------------------------ CGLS with A p and A^T r recomputed, not stored (include/trk.h)
+    def op_can_recompute(self, handle):
+        can = ctypes.c_int(0)
+        _lib.check(self.lib.trk_op_recompute_caps(handle, ctypes.byref(can)), "trk_op_recompute_caps")
+        return can.value
+
+    def op_apply_sumsq_raw(self, handle, transpose, x, partials, capacity):
+        """||Op(x)||^2 as raw block partials, nothing else written; returns their count."""
+        n = ctypes.c_int(0)
+        rc = self.lib.trk_op_apply_sumsq_raw(handle, int(bool(transpose)), x.data_ptr(), _ptr(partials), int(capacity),
+                                             ctypes.byref(n), self.stream())
+        _lib.check(rc, "trk_op_apply_sumsq_raw")
+        return n.value
+
+    def op_apply_ratio(self, handle, transpose, x, coef_on_z, sign, num, num_n, den, den_n, z, out, publish=None, publish_den=False):
+        """out = c Op(x) + z (coef_on_z false) or Op(x) + c z, c = sign * float32(S(num) / S(den)); out may be z."""
+        rc = self.lib.trk_op_apply_ratio(handle, int(bool(transpose)), x.data_ptr(), int(bool(coef_on_z)), float(sign), _ptr(num),
+                                         int(num_n), _ptr(den), int(den_n), z.data_ptr(), out.data_ptr(), _ptr(publish),
+                                         int(bool(publish_den)), self.stream())
+        _lib.check(rc, "trk_op_apply_ratio")
+
+    def cgls_recompute(self, n):
+        """1: the history-less raw-partials CGLS iteration recomputes A p and A^T r for vectors of n floats (0: off)."""
+        return int(self.lib.trk_cgls_recompute(int(n)))
+
+    def cgls_iterate_recompute(self, handle, k_first, n_iters, p, ring, s, r, X, x_prev, x_true, S, NP, np_cap, n_np, PG, PD, pcap):
+        """cgls_iterate_xbatch with the two products recomputed instead of stored (no t, no w); returns the partial-block count."""
+        c = ctypes.c_int(int(n_np))
+        rc = self.lib.trk_cgls_iterate_recompute(handle, int(k_first), int(n_iters), p.data_ptr(),
+                                                 None if ring is None else ring.data_ptr(), 0 if ring is None else ring.stride(0),
+                                                 int(s), r.data_ptr(), None, None, X.data_ptr(), X.stride(0),
+                                                 x_prev.data_ptr(), None if x_true is None else x_true.data_ptr(), _ptr(S), _ptr(NP),
+                                                 int(np_cap), ctypes.byref(c), _ptr(PG), _ptr(PD), int(pcap), self.stream())
+        _lib.check(rc, "trk_cgls_iterate_recompute")
+        return c.value
+
     def cgls_iterate_fused(self, handle, k_first, n_iters, P, R, t, w, X, keep, x_prev, x_true, S, PG, PD, pcap, NP, np_cap,
                            n_g, n_np):
         """n_iters fused (3-launch) CGLS iterations in one library call; returns (n_g, n_np)."""

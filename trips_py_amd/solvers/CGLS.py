@@ -45,12 +45,18 @@ class CGLSRun:
     `x_batch` (None: the library's rule by size, trk_cgls_x_batch; an integer s forces it): without a history, in the raw-partials
     form with grouping 1, `run()` keeps the directions of s iterations and makes their x updates in one pass
     (trk_cgls_iterate_xbatch: s - 1 of s writes of x are not made; same bits).  Costs (s - 1) * 4n bytes of device memory for the
-    directions (470 MB at 4096^2, s = 8).  `step()` keeps the one-update launches."""
+    directions (470 MB at 4096^2, s = 8).  `step()` keeps the one-update launches.
+
+    `recompute` (None: the library's rule by size, trk_cgls_recompute; True / False forces it): where the x-batch form applies (it may be
+    s = 1) and the operator can (trk_op_recompute_caps: the blur), `run()` applies A and A^T twice per iteration — once for the norm,
+    once with the r / p update as the kernel's epilogue — and never stores w = A p or t = A^T r (trk_cgls_iterate_recompute; same
+    bits in x, p, r and the scalars; `w` and `t` are then not what `step()` would have left, and nothing carries them)."""
 
     PCAP = 4096                            # room for an operator's raw block partials
     X_BATCH_MAX = 8                        # trk_cgls_xs_update takes at most 8 directions
 
-    def __init__(self, A, b, x0, max_iter, x_true=None, history=True, defer_norms=False, grouping=None, x_batch=None):
+    def __init__(self, A, b, x0, max_iter, x_true=None, history=True, defer_norms=False, grouping=None, x_batch=None,
+                 recompute=None):
         self.A = A = as_operator(A)
         self.eng = eng = A.engine
         m, n = A.shape
@@ -77,8 +83,12 @@ class CGLSRun:
         self.r, self.t, self.w, self.p = eng.empty(m), eng.empty(n), eng.empty(m), eng.empty(n)
         # x updates made s at a time (run() only): history off, raw partials, grouping 1; s - 1 more direction buffers
         self.x_batch = 1
+        self.recompute = False
         if self.raw and self.grouping == 1 and self.hist.mode == "none" and hasattr(eng, "cgls_iterate_xbatch"):
             self.x_batch = max(1, min(self.X_BATCH_MAX, int(x_batch) if x_batch is not None else eng.cgls_x_batch(n)))
+            # A p and A^T r recomputed instead of stored (run() only): the same conditions (raw implies one rank), an operator with the two forms
+            if m == n and hasattr(eng, "cgls_iterate_recompute") and eng.op_can_recompute(A._h):
+                self.recompute = bool(eng.cgls_recompute(n)) if recompute is None else bool(recompute)
         self.P_ring = eng.empty_basis(self.x_batch - 1, (n + 3) & ~3) if self.x_batch > 1 else None    # rows 16-byte aligned
         # scalar layout: S[0] = gamma_0 = ||t_0||^2 ; row k (1-based) at 5k: [delta, gamma, ||x||^2, ||dx||^2, ||x-xt||^2]
         self.S = S = eng.scalars(5 * (max_iter + 1))
@@ -169,6 +179,12 @@ class CGLSRun:
         eng = self.eng
         if self.defer and not self.dist and hasattr(self.A, "_h") and hasattr(eng, "cgls_iterate"):
             def call(k_first, n, X, keep):
+                if self.recompute:
+                    self.n_np = eng.cgls_iterate_recompute(self.A._h, k_first, n, self.p, self.P_ring, self.x_batch, self.r, X,
+                                                           self.x_cur, self.xt, self.S.ref(0), self.NP.ref(0), 1024, self.n_np,
+                                                           self.PG.ref(0), self.PD.ref(0), self.PCAP)
+                    self.x_cur = _row_of(X, k_first + n - 2, keep)
+                    return
                 if self.x_batch > 1:
                     self.n_np = eng.cgls_iterate_xbatch(self.A._h, k_first, n, self.p, self.P_ring, self.x_batch, self.r, self.t,
                                                         self.w, X, self.x_cur, self.xt, self.S.ref(0), self.NP.ref(0), 1024,
