@@ -335,7 +335,9 @@ struct SlideEpi {
 
 // RC (the large-image CGLS loop that recomputes A p and A^T r instead of storing them, trk_cgls_iterate_recompute):
 //   RC_NORM   with SUMSQ: the output is NOT stored, only its sum of squares is taken — the same qacc / ss accumulation, the same
-//             block partials as the storing kernel, entry for entry.  8n bytes become 4n.
+//             block partials as the storing kernel, entry for entry.  8n bytes become 4n.  Its time is instruction issue and load
+//             latency, not the stream, so at 9x9 it has a leaner row block (LEAN): no border rule in spans that touch no border, column
+//             pairs formed once per row, refills issued in place (see block() and the march below; docs/kernels/blur_and_cgls.md 4.1).
 //   RC_RATIO  with EPI: one coefficient of the pair is  c = sign * (float)(S(num) / S(den))  with scalar sources (a finished
 //             scalar or the block partials of an RC_NORM launch, added up by this wave as FUSE's cb is), the other is exactly 1:
 //             on_z = 0:  out = fmaf(c, A x, z)   (CGLS's r -= (gamma_old / S(delta)) (A p): fmaf(-step, w, r), k_cgls_r_update's bits)
@@ -345,7 +347,10 @@ struct SlideEpi {
 //             own four columns of its own band's rows, each D outputs before it stores that very row — no other lane, of this wave
 //             or of another, touches those entries.  Both travel in this struct and not through the kernel's __restrict__ y.
 //             `out` / `z` must not alias x (neighbouring bands read each other's halo rows of x).
-enum Rc : int { RC_NONE = 0, RC_NORM = 1, RC_RATIO = 2 };
+//   RC_NORM_LEAN  RC_NORM with the lean row block, 9x9 and not constant mode; launched where the grid gives every SIMD at most one
+//             wave (launch_slide_rc): it takes more than 256 registers, so a SIMD holds one wave of it where it holds two of RC_NORM,
+//             and a grid of two waves per SIMD runs slower with it (6144^2: 3879 -> 3816 iterations/s)
+enum Rc : int { RC_NONE = 0, RC_NORM = 1, RC_RATIO = 2, RC_NORM_LEAN = 3 };
 struct SlideRatio {
   const float* z;
   float* out;
@@ -355,6 +360,15 @@ struct SlideRatio {
   double* pub;         // may be NULL
 };
 
+// (a[1], b[0]): the pair of two neighbouring columns that straddles two register pairs, in ONE vector move.  hipcc forms such a
+// pair with two v_mov_b32 as often as with this instruction, and once per use; the norm-only pass, half of whose time is
+// instruction issue, forms each pair once per row with it (vector ALU only, no memory operand).
+__device__ __forceinline__ f2 pair_hi_lo(f2 a, f2 b) {
+  f2 d;
+  asm("v_pk_mov_b32 %0, %1, %2 op_sel:[1,0]" : "=v"(d) : "v"(a), "v"(b));
+  return d;
+}
+
 template <int KH, int KW, int D, bool SUMSQ, bool FUSE, bool EPI = false, int BC = BC_REFLECT, int RC = RC_NONE>
 __global__ __launch_bounds__(64) void k_blur_slide(const float* __restrict__ x, int64_t ldx, float* __restrict__ y,
                                                    int64_t ldy, int nx, int ny, const float* __restrict__ wts,
@@ -362,11 +376,18 @@ __global__ __launch_bounds__(64) void k_blur_slide(const float* __restrict__ x, 
                                                    int rows_per_band, SlideFuse fz, int nt_store, SlideEpi ep = SlideEpi{},
                                                    SlideRatio rq = SlideRatio{}) {
   static_assert(RC == RC_NONE || !FUSE, "the recompute forms take one operand");
-  static_assert(RC != RC_NORM || (SUMSQ && !EPI), "RC_NORM: the sum of squares alone");
+  constexpr bool NORM = RC == RC_NORM || RC == RC_NORM_LEAN;
+  static_assert(!NORM || (SUMSQ && !EPI), "RC_NORM: the sum of squares alone");
+  static_assert(RC != RC_NORM_LEAN || (KH == 9 && BC != BC_CONSTANT), "the lean norm-only form: 9x9, not constant mode");
   static_assert(RC != RC_RATIO || (EPI && !SUMSQ), "RC_RATIO: an epilogue form without a sum");
   constexpr int T = KH - 1 - KH / 2;
   constexpr int Lh = KW - 1 - KW / 2;
   constexpr int OFFC = 4 - Lh;          // v[] index of tap 0 of output column 0
+  // The norm-only pass at 9x9 has a row block of its own (see block() and the march below).  Measured at 4096^2: reflect 19.9 ->
+  // 17.5 us, nearest / mirror / wrap alike — but constant 24.0 -> 25.2 (its zero-row branch stays inside the rows) and 5x5 17.0 ->
+  // 39.3 us: with a ring of five rows the in-place refill is too late, the compiler's hoisted loads are what hides the latency
+  // there.  So constant mode and the smaller PSFs keep the row block of the storing forms.
+  constexpr bool LEAN = RC == RC_NORM_LEAN;
   constexpr int U = lcm_c(KH, D);
   static_assert(Lh <= 4 && KW / 2 <= 4, "sliding kernel handles halos of at most one 4-column group");
 
@@ -455,6 +476,19 @@ __global__ __launch_bounds__(64) void k_blur_slide(const float* __restrict__ x, 
       qR[slot] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(rin2, vr, so, 0));
     }
   };
+  // The lean norm-only form (LEAN; never constant mode, so every staged row is a row of the image) takes issue() in two steps:
+  // the byte offset of staged row t (wave-uniform scalar work, with the boundary rule's control flow), and the three loads at an
+  // offset worked out earlier
+  auto row_offset = [&](int t) {
+    int gi = first + dir * t;
+    if (!interior) gi = bmap<BC>(gi, nx);
+    return gi * rowbytes;
+  };
+  auto issue_at = [&](int so, int slot) {
+    pL[slot] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(rin, vl, so, 0));
+    pC[slot] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(rin, vc, so, 0));
+    pR[slot] = __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(rin, vr, so, 0));
+  };
 #pragma unroll
   for (int d = 0; d < D; ++d) issue(d, d);
   // EPI: coefficients (device scalars, wave-uniform) and the ring of z rows, output o in slot o % D
@@ -489,9 +523,18 @@ __global__ __launch_bounds__(64) void k_blur_slide(const float* __restrict__ x, 
   float qacc = 0.f;
 
   // One block of U staged rows.  GUARD = false is the steady state: every row refills its prefetch slot and stores one
-  // finished output row, with no bounds tests (see the loop split below).
-  auto block = [&](int t0, auto guard_tag) {
+  // finished output row, with no bounds tests (see the loop split below).  BORDER = false is the form for a span that touches
+  // neither the left nor the right border of the image: no border rule at all (LEAN only, see the march below).
+  auto block = [&](int t0, auto guard_tag, auto border_tag) __attribute__((always_inline)) {
     constexpr bool GUARD = decltype(guard_tag)::value;
+    constexpr bool BORDER = decltype(border_tag)::value;
+    // LEAN: the row offsets of the block's U refills are worked out ahead of its rows (scalar work, the only control flow of
+    // the steady state), so that the rows themselves are straight-line code
+    int so_next[LEAN ? U : 1];
+    if constexpr (LEAN) {
+#pragma unroll
+      for (int u = 0; u < U; ++u) so_next[u] = (!GUARD || t0 + u + D < total) ? row_offset(t0 + u + D) : 0;
+    }
 #pragma unroll
     for (int u = 0; u < U; ++u) {
       const int t = t0 + u;
@@ -506,8 +549,10 @@ __global__ __launch_bounds__(64) void k_blur_slide(const float* __restrict__ x, 
         if (graw >= i_begin && graw < i_end && active)                                   // first test is wave-uniform
           __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, Cv), rcomb, vst + graw * rowbytes, 0, 0);
       }
-      if (!GUARD || t + D < total) issue(t + D, slot);  // refill the slot D rows ahead
-      if constexpr (BC == BC_REFLECT) {
+      if constexpr (!LEAN)
+        if (!GUARD || t + D < total) issue(t + D, slot);  // refill the slot D rows ahead
+      if constexpr (!BORDER) {                          // an interior span: all three groups are image columns
+      } else if constexpr (BC == BC_REFLECT) {
         if (edge_span) {                                // reflect across the image's left / right border
           const f4 rev = (f4){Cv[3], Cv[2], Cv[1], Cv[0]};
           if (ledge) Lv = rev;
@@ -529,16 +574,46 @@ __global__ __launch_bounds__(64) void k_blur_slide(const float* __restrict__ x, 
           if (redge) Rv = re;
         }
       }
-      const float v[12] = {Lv[0], Lv[1], Lv[2], Lv[3], Cv[0], Cv[1], Cv[2], Cv[3], Rv[0], Rv[1], Rv[2], Rv[3]};
-      float h0 = 0.f, h1 = 0.f, h2 = 0.f, h3 = 0.f;
+      f2 hlo, hhi;
+      if constexpr (LEAN) {
+        // The same taps in the same order, on column pairs (v[j], v[j+1]): outputs 0, 1 take pair OFFC + b and outputs 2, 3
+        // pair OFFC + b + 2.  An even j is a register pair of a loaded group as it stands; an odd j straddles two and is
+        // formed ONCE per row, for both output pairs (9x9: j = 1, 3, 5, 7, 9).
+        const f2 ev[6] = {__builtin_shufflevector(Lv, Lv, 0, 1), __builtin_shufflevector(Lv, Lv, 2, 3),
+                          __builtin_shufflevector(Cv, Cv, 0, 1), __builtin_shufflevector(Cv, Cv, 2, 3),
+                          __builtin_shufflevector(Rv, Rv, 0, 1), __builtin_shufflevector(Rv, Rv, 2, 3)};
+        f2 od[5];
 #pragma unroll
-      for (int b = 0; b < KW; ++b) {
-        h0 = fmaf(wr[b], v[OFFC + b], h0);
-        h1 = fmaf(wr[b], v[OFFC + b + 1], h1);
-        h2 = fmaf(wr[b], v[OFFC + b + 2], h2);
-        h3 = fmaf(wr[b], v[OFFC + b + 3], h3);
+        for (int q = 0; q < 5; ++q)
+          if (2 * q + 1 >= OFFC && 2 * q + 1 <= OFFC + KW + 1) od[q] = pair_hi_lo(ev[q], ev[q + 1]);
+        hlo = hhi = (f2){0.f, 0.f};
+#pragma unroll
+        for (int b = 0; b < KW; ++b) {
+          const int j = OFFC + b;
+          const f2 w = {wr[b], wr[b]};
+          hlo = __builtin_elementwise_fma(w, (j & 1) ? od[j >> 1] : ev[j >> 1], hlo);
+          hhi = __builtin_elementwise_fma(w, (j & 1) ? od[(j + 2) >> 1] : ev[(j + 2) >> 1], hhi);
+        }
+      } else {
+        const float v[12] = {Lv[0], Lv[1], Lv[2], Lv[3], Cv[0], Cv[1], Cv[2], Cv[3], Rv[0], Rv[1], Rv[2], Rv[3]};
+        float h0 = 0.f, h1 = 0.f, h2 = 0.f, h3 = 0.f;
+#pragma unroll
+        for (int b = 0; b < KW; ++b) {
+          h0 = fmaf(wr[b], v[OFFC + b], h0);
+          h1 = fmaf(wr[b], v[OFFC + b + 1], h1);
+          h2 = fmaf(wr[b], v[OFFC + b + 2], h2);
+          h3 = fmaf(wr[b], v[OFFC + b + 3], h3);
+        }
+        hlo = (f2){h0, h1};
+        hhi = (f2){h2, h3};
       }
-      const f2 hlo = {h0, h1}, hhi = {h2, h3};
+      if constexpr (LEAN) {
+        // The refill goes out here, behind the last use of the slot's old row, and nothing is scheduled across this point: the
+        // load then lands in the registers it replaces.  Issued ahead of the horizontal pass, as in the storing forms, it
+        // needs registers of its own and the ring is copied back into place at the end of every block (28 64-bit moves).
+        __builtin_amdgcn_sched_barrier(0);
+        if (!GUARD || t + D < total) issue_at(so_next[u], slot);
+      }
       // scatter into the rolling accumulators: output o = t - a gets wc[a] * h_t
 #pragma unroll
       for (int a = 0; a < KH; ++a) {
@@ -581,10 +656,10 @@ __global__ __launch_bounds__(64) void k_blur_slide(const float* __restrict__ x, 
         // NOTE the row offset goes into the VGPR offset, not the SGPR soffset: with an SGPR soffset hipcc (ROCm 7.2)
         // emits no wait state between a >64-bit buffer store and a VALU overwrite of its data registers, and on
         // gfx950 the last dword of the store was then observed corrupted (lanes 12-15 of each row of 16).
-        if (active) {
+        if (!BORDER || active) {                        // (every lane of an interior span is active)
           // aux = 2: non-temporal store, for images too large for the next kernel to find the output cached
           // (stream_nontemporal(); 4096^2: 23.9 -> 23.2 us in the CGLS loop); nt_store is grid-uniform
-          if constexpr (RC != RC_NORM) {
+          if constexpr (!NORM) {
             if (nt_store & 1)
               __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u4, out), rout, vst + (ofirst + dir * o) * rowbytes, 0, 2);
             else
@@ -601,10 +676,21 @@ __global__ __launch_bounds__(64) void k_blur_slide(const float* __restrict__ x, 
   };
   // first block (outputs start after KH-1 rows) and last block (prefetch stops) are guarded; the middle is not:
   // for t < total - U:  t + D < total  and  o = t - (KH-1) < band_rows  hold by construction, o >= 0 after block 0.
-  block(0, std::true_type{});
-  int t0 = U;
-  for (; t0 + U < total; t0 += U) block(t0, std::false_type{});
-  if (t0 < total) block(t0, std::true_type{});
+  auto march = [&](auto border_tag) __attribute__((always_inline)) {
+    block(0, std::true_type{}, border_tag);
+    int t0 = U;
+    for (; t0 + U < total; t0 += U) block(t0, std::false_type{}, border_tag);
+    if (t0 < total) block(t0, std::true_type{}, border_tag);
+  };
+  // The norm-only pass spends half its time issuing vector instructions, and the border rule is per-row selects that only the
+  // first and the last span of a row of spans need: branch once (wave-uniform) to a march without it.  Wrap has no rule in the loop (its
+  // edge lanes load the far end of the row).  The storing forms are bound by the stream and keep the one march.
+  if constexpr (LEAN && BC != BC_WRAP) {
+    if (edge_span) march(std::true_type{});
+    else march(std::false_type{});
+  } else {
+    march(std::true_type{});
+  }
   if (SUMSQ) ss += (double)qacc;
   if (SUMSQ) {
     ss = wave_sum(ss);
@@ -905,8 +991,17 @@ int launch_slide_rc(const BlurImpl* im, int tr, const float* x, double* part, co
   if (rq)   // plain stores (nt_store = 0): the output is read again by the two launches that follow; stored non-temporally as the plain
             // blur's output is from 11 M unknowns, the loop at 4096^2 ran at 8.43 k iterations/s instead of 8.85 k
     hipExtLaunchKernelGGL((k_blur_slide<K, K, D, false, false, true, BC, RC_RATIO>), grid, block, 0, s, ev0, ev1, 0, x, 0, rq->out, 0, im->nx, im->ny, w, part, spans_x, nbands, rows_per_band, nofuse, 0, SlideEpi{}, *rq);
-  else
-    hipExtLaunchKernelGGL((k_blur_slide<K, K, D, true, false, false, BC, RC_NORM>), grid, block, 0, s, ev0, ev1, 0, x, 0, (float*)nullptr, 0, im->nx, im->ny, w, part, spans_x, nbands, rows_per_band, nofuse, 0, SlideEpi{}, SlideRatio{});
+  else {
+    // the lean form where no SIMD gets a second wave (see RC_NORM_LEAN); same grid, same partials either way
+    bool lean = false;
+    if constexpr (K == 9 && BC != BC_CONSTANT) lean = spans_x * nbands <= 4 * cu_count();
+    if constexpr (K == 9 && BC != BC_CONSTANT) {
+      if (lean)
+        hipExtLaunchKernelGGL((k_blur_slide<K, K, D, true, false, false, BC, RC_NORM_LEAN>), grid, block, 0, s, ev0, ev1, 0, x, 0, (float*)nullptr, 0, im->nx, im->ny, w, part, spans_x, nbands, rows_per_band, nofuse, 0, SlideEpi{}, SlideRatio{});
+    }
+    if (!lean)
+      hipExtLaunchKernelGGL((k_blur_slide<K, K, D, true, false, false, BC, RC_NORM>), grid, block, 0, s, ev0, ev1, 0, x, 0, (float*)nullptr, 0, im->nx, im->ny, w, part, spans_x, nbands, rows_per_band, nofuse, 0, SlideEpi{}, SlideRatio{});
+  }
   TRK_LAUNCH_CHECK();
   return TRK_OK;
 }
