@@ -76,6 +76,26 @@ int trk_device_info(int* cu_count, int* wavefront, int64_t* lds_per_cu, int64_t*
 int trk_blur2d_create(const double* psf_host, int kh, int kw, int nx, int ny, trk_op** out);
 int trk_blur2d_create_bc(const double* psf_host, int kh, int kw, int nx, int ny, int boundary, trk_op** out);
 
+/* Which kernel a blur runs on.  Separable odd square PSFs up to 9x9 on whole 4-column groups take the sliding kernel, the other odd
+ * square PSFs up to 15x15 the LDS strip kernel — as before; every other PSF up to 64x64 (even, rectangular, measured, defocus,
+ * motion) the LDS tile kernel, in its separable form (kh + kw multiply-adds per pixel) when the PSF is rank 1, else in the direct
+ * form, whose sums are the generic kernel's bit for bit; a side above 64 the generic kernel.
+ * trk_blur2d_plan: that rule for a kh x kw PSF (separable: rank 1 or not) on an nx x ny image — pure host logic, no device.
+ * trk_blur2d_path: the path of a contiguous, 16-byte-aligned one-vector apply of this handle (an unaligned or oddly strided operand
+ *   of a slide shape takes the strip kernel), and whether the PSF passed the rank-1 test at creation.
+ * trk_blur2d_set_path: force TILE (any PSF up to 64x64, slide and strip shapes included; TRK_EUNSUPPORTED above) or GENERIC, or go
+ *   back to the rule with AUTO; SLIDE, STRIP and unknown values are TRK_EINVAL.  A forced handle has none of the sliding kernel's
+ *   optional forms: trk_op_fused_caps, trk_op_axpby_caps, trk_op_recompute_caps and trk_cgls_tiled_caps report 0 and the callers'
+ *   fallbacks run.  For tests and rate measurements.  A handle that is not a blur: TRK_EINVAL. */
+#define TRK_BLUR_PATH_AUTO 0
+#define TRK_BLUR_PATH_SLIDE 1
+#define TRK_BLUR_PATH_STRIP 2
+#define TRK_BLUR_PATH_TILE 3
+#define TRK_BLUR_PATH_GENERIC 4
+int trk_blur2d_plan(int kh, int kw, int separable, int nx, int ny, int* path);
+int trk_blur2d_path(const trk_op* op, int* path, int* separable);
+int trk_blur2d_set_path(trk_op* op, int path);
+
 /* Parallel-beam Radon transform, Joseph / linear-interpolation projector, matched adjoint.
  * Replaces astra.OpTomo over create_proj_geom('parallel', 1, N, theta) + 'linear' projector and
  * the /N scaling of trips/utilities/io.py:392-399.  Image N x N row-major; sinogram

@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB_PATH = os.path.join(CSRC, "libtrk.so")
-SOURCES = ["core.hip", "vecops.hip", "blur2d.hip", "gemv.hip", "wgram.hip", "tvops.hip", "radon2d.hip", "radon_fwd.hip", "radon_adj.hip", "spmv.hip", "framelet2d.hip", "fanbeam2d.hip", "projected.hip", "host_regparam.hip", "host_worker.hip", "hybrid_host.hip", "cgls_update.hip", "cgls_loop.hip", "comm.hip", "cgls_tiled.hip", "cgls_sharded.hip", "ref64.hip", "dense_svd.hip"]
+SOURCES = ["core.hip", "vecops.hip", "blur2d.hip", "blur_tile.hip", "gemv.hip", "wgram.hip", "tvops.hip", "radon2d.hip", "radon_fwd.hip", "radon_adj.hip", "spmv.hip", "framelet2d.hip", "fanbeam2d.hip", "projected.hip", "host_regparam.hip", "host_worker.hip", "hybrid_host.hip", "cgls_update.hip", "cgls_loop.hip", "comm.hip", "cgls_tiled.hip", "cgls_sharded.hip", "ref64.hip", "dense_svd.hip"]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-I" + INCLUDE, "-I" + CSRC]
 
 
@@ -137,6 +137,9 @@ SIGNATURES = {
     "trk_device_info": (c_int, [ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
     "trk_blur2d_create": (c_int, [ctypes.POINTER(c_dbl), c_int, c_int, c_int, c_int, ctypes.POINTER(c_op)]),
     "trk_blur2d_create_bc": (c_int, [ctypes.POINTER(c_dbl), c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_op)]),
+    "trk_blur2d_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)]),
+    "trk_blur2d_path": (c_int, [c_op, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+    "trk_blur2d_set_path": (c_int, [c_op, c_int]),
     "trk_radon2d_create": (c_int, [c_int, c_int, ctypes.POINTER(c_dbl), c_int, c_dbl, ctypes.POINTER(c_op)]),
     "trk_radon2d_dynamic_create": (c_int, [c_int, c_int, ctypes.POINTER(c_dbl), c_int, c_int, c_dbl, ctypes.POINTER(c_op)]),
     "trk_fanbeam2d_create": (c_int, [c_int, c_int, c_dbl, c_dbl, c_dbl, ctypes.POINTER(c_dbl), c_int, ctypes.POINTER(c_op)]),

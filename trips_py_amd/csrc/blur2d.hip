@@ -18,6 +18,7 @@
 //     PSFs: the direct KH*KW form from the same 12 floats).  Stores are 16-byte coalesced.  Optionally sum(y^2) is
 //     accumulated per thread in fp64 over all steps and reduced once per workgroup (wave64 shuffles).
 //   * grid = strips x row bands, sized to ~4 workgroups per CU so that a 4096^2 image is split evenly (no tail).
+//   * k_blur_tile (blur_tile.hip): any PSF up to 64x64 — even, rectangular, non-separable — from an LDS window.
 //   * k_blur_generic: any PSF size (even, rectangular, longer than the image: repeated extension), no tiling.
 //
 // Boundary modes (trk.h TRK_BOUNDARY_*): the index map of an out-of-image sample is a compile-time parameter BC of every
@@ -28,7 +29,7 @@
 // The reflect instantiations are the code that existed before the modes did (bmap<BC_REFLECT> == reflect()).  The "transpose"
 // is the flipped-PSF convolution in the same mode, as in the reference: the exact adjoint only for reflect / constant / wrap
 // with an odd symmetric PSF.
-#include "trk_internal.h"
+#include "blur_internal.h"
 #include <hip/hip_ext.h>
 
 #include <cmath>
@@ -43,76 +44,6 @@ namespace {
 constexpr int NT = 256;
 constexpr int TW = 128;  // output tile width  (32 lanes x float4)
 constexpr int TH = 32;   // output tile height (8 thread rows x 4)
-
-typedef float f4 __attribute__((ext_vector_type(4)));  // one 16-byte register quad: keeps loads/stores as b128
-
-__host__ __device__ constexpr int rup4(int v) { return (v + 3) & ~3; }
-
-__device__ __forceinline__ int reflect(int i, int n) {
-  // half-sample symmetric extension, any distance; in-range indices (the common case) skip the division
-  if ((unsigned)i < (unsigned)n) return i;
-  const int p = 2 * n;
-  i %= p;
-  if (i < 0) i += p;
-  return (i >= n) ? (p - 1 - i) : i;
-}
-
-// boundary modes: the values of trk.h's TRK_BOUNDARY_*
-enum Bc : int { BC_REFLECT = 0, BC_CONSTANT = 1, BC_NEAREST = 2, BC_MIRROR = 3, BC_WRAP = 4 };
-
-// image index of sample i of a length-n line extended by mode BC, at any distance; -1 for a constant-mode sample outside
-// (the caller reads 0 there and forms no address)
-template <int BC>
-__device__ __forceinline__ int bmap(int i, int n) {
-  if constexpr (BC == BC_REFLECT) {
-    return reflect(i, n);
-  } else {
-    if ((unsigned)i < (unsigned)n) return i;
-    if constexpr (BC == BC_CONSTANT) {
-      return -1;
-    } else if constexpr (BC == BC_NEAREST) {
-      return i < 0 ? 0 : n - 1;
-    } else if constexpr (BC == BC_WRAP) {
-      i %= n;
-      return i < 0 ? i + n : i;
-    } else {   // BC_MIRROR: whole-sample symmetric, period 2n-2 (n = 1: the one sample)
-      if (n == 1) return 0;
-      const int p = 2 * n - 2;
-      i %= p;
-      if (i < 0) i += p;
-      return (i >= n) ? (p - i) : i;
-    }
-  }
-}
-
-// one sample of row `row` (length n) at column j under mode BC
-template <int BC>
-__device__ __forceinline__ float bload(const float* row, int j, int n) {
-  const int g = bmap<BC>(j, n);
-  if constexpr (BC == BC_CONSTANT)
-    if (g < 0) return 0.f;
-  return row[g];
-}
-
-template <class F>
-int bc_dispatch(int bc, F&& f) {   // run f with the mode as a compile-time constant
-  switch (bc) {
-    case BC_CONSTANT: return f(std::integral_constant<int, BC_CONSTANT>{});
-    case BC_NEAREST: return f(std::integral_constant<int, BC_NEAREST>{});
-    case BC_MIRROR: return f(std::integral_constant<int, BC_MIRROR>{});
-    case BC_WRAP: return f(std::integral_constant<int, BC_WRAP>{});
-    default: return f(std::integral_constant<int, BC_REFLECT>{});
-  }
-}
-
-struct BlurImpl {
-  int nx, ny, kh, kw;
-  int bc;              // boundary mode (Bc)
-  bool separable;
-  bool tiled;          // a k_blur_strip instantiation exists for (kh,kw)
-  float* w_dev[2];     // [kh*kw] correlation weights: 0 forward, 1 "transpose" (flipped PSF)
-  float* sep_dev[2];   // [kw row weights | kh column weights]
-};
 
 // ------------------------------------------------------------------------------------------------ strip kernel
 // min waves per SIMD asked of the register allocator: 4 (= 4 workgroups per CU) for the separable kernels up to 9x9,
@@ -729,18 +660,6 @@ __global__ __launch_bounds__(NT) void k_blur_generic(const float* __restrict__ x
 }
 
 // ------------------------------------------------------------------------------------------------ dispatch
-// strips x row bands: about 4 workgroups per CU, bands a whole number of 32-row steps
-inline void strip_grid(int nx, int ny, int batch, int* strips_x, int* rows_per_band, int* nband) {
-  const int sx = ceil_div(ny, TW), steps = ceil_div(nx, TH);
-  int want = (4 * cu_count()) / (sx * (batch > 0 ? batch : 1));
-  if (want < 1) want = 1;
-  if (want > steps) want = steps;
-  const int steps_per_band = ceil_div(steps, want);
-  *strips_x = sx;
-  *rows_per_band = steps_per_band * TH;
-  *nband = ceil_div(nx, *rows_per_band);
-}
-
 template <int K, int BC>
 int launch_strip(const BlurImpl* im, int tr, const float* x, int64_t ldx, float* y, int64_t ldy, int batch,
                  double* part, int strips_x, int rows_per_band, int nband, hipStream_t s) {
@@ -825,9 +744,14 @@ inline void slide_grid(int nx, int ny, int batch, int kh, int U, int* spans_x, i
   *rows_per_band = rpb;
 }
 
+// the kernel a contiguous, aligned one-vector apply of this handle runs on (TRK_BLUR_PATH_*)
+inline int blur_path(const BlurImpl* im) {
+  return im->forced != TRK_BLUR_PATH_AUTO ? im->forced : blur_plan(im->kh, im->kw, im->separable, im->nx, im->ny);
+}
+
+// the sliding kernel serves this handle (never a handle forced to another path: trk_blur2d_set_path)
 inline bool slide_shape_ok(const BlurImpl* im) {
-  return im->separable && im->kh == im->kw && (im->kh & 1) && im->kh >= 3 && im->kh <= 9 && (im->ny & 3) == 0 &&
-         im->ny >= 8 && (int64_t)im->nx * im->ny < ((int64_t)1 << 29);   // byte offsets are 32-bit signed ints in the kernel
+  return im->forced == TRK_BLUR_PATH_AUTO && blur_slide_shape(im->kh, im->kw, im->separable, im->nx, im->ny);
 }
 
 // y = A (x1 + cb * x2), comb written out, sum(y^2) as raw partials (CGLS fast path; 9x9-class separable PSFs only)
@@ -870,9 +794,14 @@ int blur_apply(trk_op* op, int tr, const float* x, int64_t ldx, float* y, int64_
   auto* im = static_cast<BlurImpl*>(op->impl);
   double* part = nullptr;
   int nblk;
-  const bool slide_ok = slide_shape_ok(im) && aligned16(x) && aligned16(y) &&
-                        (batch == 1 || ((ldx & 3) == 0 && (ldy & 3) == 0));
-  if (slide_ok) {
+  // the path: the handle's forced one, else the rule of trk_blur2d_plan; a slide shape whose operands are not 16-byte aligned
+  // (or sit at a leading dimension that is no multiple of 4) takes the strip kernel, which serves every slide shape
+  int path = blur_path(im);
+  if (path == TRK_BLUR_PATH_SLIDE &&
+      !(aligned16(x) && aligned16(y) && (batch == 1 || ((ldx & 3) == 0 && (ldy & 3) == 0))))
+    path = TRK_BLUR_PATH_STRIP;
+  if (path == TRK_BLUR_PATH_TILE) return blur_tile_apply(op, im, tr, x, ldx, y, ldy, batch, sumsq, s);
+  if (path == TRK_BLUR_PATH_SLIDE) {
     int spans_x, nbands, rpb;
     const int Usel = (im->kh == 9) ? 9 : (im->kh == 7) ? 7 : (im->kh == 5) ? 5 : 6;   // lcm(KH, D) of the instantiations below
     slide_grid(im->nx, im->ny, batch, im->kh, Usel, &spans_x, &nbands, &rpb);
@@ -899,9 +828,9 @@ int blur_apply(trk_op* op, int tr, const float* x, int64_t ldx, float* y, int64_
     if (sumsq) return finalize_sums(part, nblk * batch, 1, 1, sumsq, s);
     return TRK_OK;
   }
-  if (im->tiled) {
+  if (path == TRK_BLUR_PATH_STRIP) {
     int strips_x, rows_per_band, nband;
-    strip_grid(im->nx, im->ny, batch, &strips_x, &rows_per_band, &nband);
+    strip_grid(im->nx, im->ny, batch, TW, TH, &strips_x, &rows_per_band, &nband);
     nblk = strips_x * nband;
     if (sumsq)
       if (int rc = scratch_doubles(s, (size_t)nblk * batch, &part)) return rc;
@@ -1047,6 +976,16 @@ int blur_apply_ratio(trk_op* op, int tr, const float* x, const RatioCoef& c, con
   return blur_apply_rc(op, tr, x, nullptr, 0, nullptr, &rq, s);
 }
 
+// the optional forms of a blur handle (fused operand, axpby epilogue, recompute pair): the sliding kernel's, so a handle has them
+// exactly when that kernel serves it — a handle forced to another path has none, and its callers take their fallbacks
+void blur_set_forms(trk_op* op) {
+  const bool slide = slide_shape_ok(static_cast<BlurImpl*>(op->impl));
+  op->apply_fused = slide ? blur_apply_fused : nullptr;
+  op->apply_axpby_plain = slide ? blur_apply_axpby_plain : nullptr;
+  op->apply_norm = slide ? blur_apply_norm : nullptr;
+  op->apply_ratio = slide ? blur_apply_ratio : nullptr;
+}
+
 void blur_destroy(trk_op* op) {
   auto* im = static_cast<BlurImpl*>(op->impl);
   for (int t = 0; t < 2; ++t) {
@@ -1066,6 +1005,7 @@ bool blur_separable_params(trk_op* op, int* nx, int* ny, int* kh, int* kw, const
   if (!op || op->kind != 1) return false;
   auto* im = static_cast<BlurImpl*>(op->impl);
   if (!im->separable || !im->sep_dev[0] || !im->sep_dev[1]) return false;
+  if (im->forced != TRK_BLUR_PATH_AUTO) return false;   // a forced handle runs its own kernel only
   if (boundary) *boundary = im->bc;
   *nx = im->nx;
   *ny = im->ny;
@@ -1089,7 +1029,7 @@ extern "C" int trk_blur2d_create_bc(const double* psf, int kh, int kw, int nx, i
   static_assert(TRK_BOUNDARY_REFLECT == BC_REFLECT && TRK_BOUNDARY_CONSTANT == BC_CONSTANT && TRK_BOUNDARY_NEAREST == BC_NEAREST &&
                     TRK_BOUNDARY_MIRROR == BC_MIRROR && TRK_BOUNDARY_WRAP == BC_WRAP,
                 "blur2d boundary modes follow trk.h");
-  auto* im = new BlurImpl{nx, ny, kh, kw, boundary, false, false, {nullptr, nullptr}, {nullptr, nullptr}};
+  auto* im = new BlurImpl{nx, ny, kh, kw, boundary, false, false, {nullptr, nullptr}, {nullptr, nullptr}, TRK_BLUR_PATH_AUTO};
 
   // correlation weights: forward c[a'][b'] = psf[kh-1-a'][kw-1-b'];  "transpose" convolves with flip(psf): c = psf
   std::vector<float> wf((size_t)kh * kw), wt((size_t)kh * kw);
@@ -1123,7 +1063,7 @@ extern "C" int trk_blur2d_create_bc(const double* psf, int kh, int kw, int nx, i
         }
   }
   im->separable = sep;
-  im->tiled = (kh == kw) && (kh & 1) && kh >= 3 && kh <= 15;
+  im->tiled = blur_strip_shape(kh, kw);
 
   auto upload = [](const std::vector<float>& h, float** d) -> int {
     TRK_HIP(hipMalloc(d, h.size() * sizeof(float)));
@@ -1152,12 +1092,39 @@ extern "C" int trk_blur2d_create_bc(const double* psf, int kh, int kw, int nx, i
   }
   const int64_t n = (int64_t)nx * ny;
   auto* op = new trk_op{1, n, n, im, blur_apply, blur_destroy, nullptr, 0};
-  if (slide_shape_ok(im)) op->apply_fused = blur_apply_fused;
-  if (slide_shape_ok(im)) op->apply_axpby_plain = blur_apply_axpby_plain;
-  if (slide_shape_ok(im)) {
-    op->apply_norm = blur_apply_norm;
-    op->apply_ratio = blur_apply_ratio;
-  }
+  blur_set_forms(op);
   *out = op;
+  return TRK_OK;
+}
+
+extern "C" int trk_blur2d_plan(int kh, int kw, int separable, int nx, int ny, int* path) {
+  TRK_REQUIRE(path, "trk_blur2d_plan: NULL argument");
+  TRK_REQUIRE(kh >= 1 && kw >= 1 && nx >= 1 && ny >= 1, "trk_blur2d_plan: sizes must be >= 1");
+  *path = blur_plan(kh, kw, separable != 0, nx, ny);
+  return TRK_OK;
+}
+
+extern "C" int trk_blur2d_path(const trk_op* op, int* path, int* separable) {
+  TRK_REQUIRE(op && path && separable, "trk_blur2d_path: NULL argument");
+  TRK_REQUIRE(op->kind == 1, "trk_blur2d_path: not a blur handle");
+  const auto* im = static_cast<const BlurImpl*>(op->impl);
+  *path = blur_path(im);
+  *separable = im->separable ? 1 : 0;
+  return TRK_OK;
+}
+
+extern "C" int trk_blur2d_set_path(trk_op* op, int path) {
+  TRK_REQUIRE(op, "trk_blur2d_set_path: NULL argument");
+  TRK_REQUIRE(op->kind == 1, "trk_blur2d_set_path: not a blur handle");
+  TRK_REQUIRE(path == TRK_BLUR_PATH_AUTO || path == TRK_BLUR_PATH_TILE || path == TRK_BLUR_PATH_GENERIC,
+              "trk_blur2d_set_path: path %d cannot be forced (AUTO, TILE or GENERIC)", path);
+  auto* im = static_cast<BlurImpl*>(op->impl);
+  if (path == TRK_BLUR_PATH_TILE && (im->kh > kBlurTileMaxSide || im->kw > kBlurTileMaxSide))
+    return fail(TRK_EUNSUPPORTED, "trk_blur2d_set_path: the tile kernel takes PSFs up to %dx%d, this one is %dx%d", kBlurTileMaxSide,
+                kBlurTileMaxSide, im->kh, im->kw);
+  im->forced = path;
+  blur_set_forms(op);
+  free(op->aux);            // a consumer's per-handle cache (the tiled CGLS's geometry) was made for the path before
+  op->aux = nullptr;
   return TRK_OK;
 }

@@ -222,7 +222,16 @@ class Blur2D(_HandleOperator):
     boundary: 'reflect' (default), 'constant' (zero fill), 'nearest', 'mirror', 'wrap', or scipy's aliases 'grid-mirror',
     'grid-constant', 'grid-wrap'; `self.boundary` holds the canonical name.  The flipped-PSF "transpose" is the exact adjoint
     only for an odd-sized point-symmetric PSF under 'reflect', 'constant' or 'wrap'.  Under 'nearest' / 'mirror', or with an
-    even-sized PSF in any mode, it differs from A^T in entries next to the border, as the reference's does."""
+    even-sized PSF in any mode, it differs from A^T in entries next to the border, as the reference's does.
+
+    `path` names the kernel a plain apply runs on: 'slide' (separable odd PSFs up to 9x9), 'strip' (odd square PSFs up to 15x15),
+    'tile' (every other PSF up to 64x64: even, rectangular, wide Gaussians, defocus, motion, measured) or 'generic' (a side above
+    64); `set_path` forces 'tile' or 'generic' for tests and rate measurements.
+
+    `streaming` stays `max(psf.shape) <= 15`, whatever the path: it makes GKS / MMGKS re-apply A instead of storing A V, which
+    pays for the memory-bound slide and strip kernels only — a tile-path blur is bound by its multiply-adds, not by its bytes."""
+
+    PATHS = {"auto": 0, "slide": 1, "strip": 2, "tile": 3, "generic": 4}          # trk.h TRK_BLUR_PATH_*
 
     def __init__(self, psf, nx, ny, engine=None, boundary="reflect"):
         self.boundary = normalize_boundary(boundary)       # (a bad name fails before any device is touched)
@@ -237,6 +246,21 @@ class Blur2D(_HandleOperator):
                                                    ctypes.byref(h)), "trk_blur2d_create_bc")
         super().__init__(h, engine)
         self.streaming = max(psf.shape) <= 15          # the sliding-window / LDS-strip kernels (csrc/blur2d.hip)
+
+    @property
+    def path(self):
+        """'slide' | 'strip' | 'tile' | 'generic': the kernel of a contiguous, 16-byte-aligned one-vector apply (trk_blur2d_path)."""
+        path, sep = ctypes.c_int(0), ctypes.c_int(0)
+        _lib.check(self.engine.lib.trk_blur2d_path(self._h, ctypes.byref(path), ctypes.byref(sep)), "trk_blur2d_path")
+        return {v: k for k, v in self.PATHS.items()}[path.value]
+
+    def set_path(self, name):
+        """Force the kernel: 'tile' (any PSF up to 64x64; NotImplementedError above), 'generic', or 'auto' for the rule again.  A
+        forced operator has no fused / epilogue / recompute forms: the solvers take their plain loops (trk_blur2d_set_path)."""
+        if name not in ("auto", "tile", "generic"):
+            raise ValueError(f"set_path: expected 'auto', 'tile' or 'generic', got {name!r}")
+        _lib.check(self.engine.lib.trk_blur2d_set_path(self._h, self.PATHS[name]), "trk_blur2d_set_path")
+        return self
 
 
 class Blur1D(Blur2D):

@@ -3,6 +3,9 @@
 
   gauss_psf(dim, spread)              <- Deblurring2D.Gauss            trips/test_problems/Deblurring2D.py:48-64
   gauss_psf_1d(n, sigma)              <- Deblurring1D.Gauss1D          trips/test_problems/Deblurring1D.py:63-69
+  Deblurring1D().Defocus1D(n, r)      <- Deblurring1D.Defocus1D        trips/test_problems/Deblurring1D.py:70-82
+  defocus_psf(dim, radius)            out-of-focus blur: a uniform disc (an extension; on gauss_psf's grid)
+  motion_psf(dim, length, angle_deg)  linear motion blur: a line segment, bilinear deposits (an extension)
   Deblurring2D().forward_Op(...)      <- Deblurring2D.forward_Op       :66-73   (returns a trips_py_amd Blur2D)
   synthetic_image / add_noise         seeded versions of the data recipe (:141-146): what bench.py / smoke() / the tests use
 
@@ -37,8 +40,50 @@ def gauss_psf_1d(n, sigma):
     return psf / psf.sum()
 
 
+def defocus_psf(dim, radius):
+    """Out-of-focus blur: 1 where X^2 + Y^2 <= radius^2 on gauss_psf's grid (arange(-fix(k/2), ceil(k/2)) per axis), 0 elsewhere,
+    normalised to sum 1.  Returns (psf, center) with center = [fix(m/2), fix(n/2)], the grid's origin."""
+    m, n = int(dim[0]), int(dim[1])
+    radius = float(radius)
+    if radius < 0:
+        raise ValueError(f"defocus_psf: radius must be >= 0, got {radius!r}")
+    xs = np.arange(-np.fix(n / 2), np.ceil(n / 2))
+    ys = np.arange(-np.fix(m / 2), np.ceil(m / 2))
+    X, Y = np.meshgrid(xs, ys)
+    psf = (X ** 2 + Y ** 2 <= radius ** 2).astype(np.float64)
+    psf /= psf.sum()
+    return psf, np.array([int(np.fix(m / 2)), int(np.fix(n / 2))])
+
+
+def motion_psf(dim, length, angle_deg):
+    """Linear motion blur: a segment of `length` pixels through the centre [fix(m/2), fix(n/2)], at `angle_deg` counter-clockwise
+    from the column axis (rows go down).  S = max(2, 4 ceil(length) + 1) points t uniform on [-length/2, length/2] sit at
+    (c0 - t sin(a), c1 + t cos(a)); each deposits its bilinear weights on its four neighbours; float64 throughout, normalised to
+    sum 1.  A point with a neighbour outside the array raises ValueError (the PSF array is too small for the segment).
+    Returns (psf, center)."""
+    m, n = int(dim[0]), int(dim[1])
+    length = float(length)
+    if length < 0:
+        raise ValueError(f"motion_psf: length must be >= 0, got {length!r}")
+    c0, c1 = int(np.fix(m / 2)), int(np.fix(n / 2))
+    a = np.deg2rad(float(angle_deg))
+    t = np.linspace(-length / 2, length / 2, max(2, 4 * int(np.ceil(length)) + 1))
+    rows, cols = c0 - t * np.sin(a), c1 + t * np.cos(a)
+    i0, j0 = np.floor(rows).astype(int), np.floor(cols).astype(int)
+    fi, fj = rows - i0, cols - j0
+    psf = np.zeros((m, n), dtype=np.float64)
+    for di, dj, wgt in ((0, 0, (1 - fi) * (1 - fj)), (0, 1, (1 - fi) * fj), (1, 0, fi * (1 - fj)), (1, 1, fi * fj)):
+        ii, jj = i0 + di, j0 + dj
+        if ii.min() < 0 or jj.min() < 0 or ii.max() >= m or jj.max() >= n:
+            raise ValueError(f"motion_psf: a {length} pixel segment at {angle_deg} degrees does not fit a {m}x{n} PSF")
+        np.add.at(psf, (ii, jj), wgt)
+    psf /= psf.sum()
+    return psf, np.array([c0, c1])
+
+
 class Deblurring2D:
-    """Operator-constructor subset of trips.test_problems.Deblurring2D (same method names)."""
+    """Operator-constructor subset of trips.test_problems.Deblurring2D (same method names), with two PSFs beside the reference's
+    Gaussian: Defocus and Motion."""
 
     def __init__(self, **kwargs):
         self.nx = self.ny = None
@@ -48,10 +93,32 @@ class Deblurring2D:
         self.dim, self.spread = PSFdim, PSFspread
         return gauss_psf(PSFdim, PSFspread)
 
-    def forward_Op(self, dim, spread, nx, ny, engine=None, boundary_condition="reflect"):
-        """boundary_condition (an extension: the reference's 2-D blur is always 'reflect'): any mode Blur2D accepts."""
+    def Defocus(self, PSFdim, radius):
+        self.dim, self.spread = PSFdim, radius
+        return defocus_psf(PSFdim, radius)
+
+    def Motion(self, PSFdim, length, angle):
+        self.dim, self.spread = PSFdim, (length, angle)
+        return motion_psf(PSFdim, length, angle)
+
+    def forward_Op(self, dim, spread, nx, ny, engine=None, boundary_condition="reflect", psf_type="gauss"):
+        """boundary_condition (an extension: the reference's 2-D blur is always 'reflect'): any mode Blur2D accepts.
+        psf_type (an extension): 'gauss' (the reference's PSF, the default), 'defocus' (spread is the radius), 'motion' (spread
+        is (length, angle in degrees)), or a 2-D array taken as the PSF itself (dim and spread are then not used)."""
         self.nx, self.ny = nx, ny
-        psf, _ = self.Gauss(dim, spread)
+        if isinstance(psf_type, str):
+            if psf_type == "gauss":
+                psf, _ = self.Gauss(dim, spread)
+            elif psf_type == "defocus":
+                psf, _ = self.Defocus(dim, spread)
+            elif psf_type == "motion":
+                psf, _ = self.Motion(dim, spread[0], spread[1])
+            else:
+                raise ValueError(f"forward_Op: psf_type must be 'gauss', 'defocus', 'motion' or a 2-D array, got {psf_type!r}")
+        else:
+            psf = np.asarray(psf_type, dtype=np.float64)
+            if psf.ndim != 2:
+                raise ValueError("forward_Op: a PSF given as an array must be 2-D")
         return Blur2D(psf, nx, ny, engine=engine, boundary=boundary_condition)
 
 
@@ -67,6 +134,21 @@ class Deblurring1D:
         self.grid_points = grid_points
         psf = gauss_psf_1d(grid_points, parameter)
         return psf, int(np.where(psf == psf.max())[0][0])
+
+    def Defocus1D(self, grid_points, parameter):
+        """The reference's 1-D out-of-focus PSF (Deblurring1D.py:70-82), quirk included: the array RETURNED is the un-normalised
+        one, 1 / (pi parameter^2) where (i + 1 - center)^2 <= parameter^2; the normalised PSF is stored in self.PSF."""
+        self.grid_points = grid_points
+        center = np.intp(np.fix(int(grid_points / 2)))
+        if parameter == 0:
+            PSF = np.zeros(grid_points)
+            PSF[center] = 1
+            self.PSF = PSF
+        else:
+            PSF = np.ones(grid_points) / (np.pi * parameter ** 2)
+            PSF[(np.arange(1, grid_points + 1) - center) ** 2 > parameter ** 2] = 0
+            self.PSF = PSF / PSF.sum()
+        return PSF, center
 
     def forward_Op_1D(self, parameter, nx, boundary_condition="reflect", engine=None):
         """boundary_condition: the scipy.ndimage mode of the forward convolve1d and of the flipped-PSF "transpose" (:56-62) —
