@@ -269,6 +269,86 @@ class Radon2D(_Op):
             self._M = sp.csr_matrix((val.reshape(-1), idx.reshape(-1), indptr), shape=self.shape)
         return self._M
 
+    def _mode(self, a):
+        """(row-marching?, cos, sin, 1/|cos| or 1/|sin|) of angle a, as matrix() decides and forms them."""
+        ct, st = np.cos(self.angles[a]), np.sin(self.angles[a])
+        rows = abs(ct) >= abs(st)
+        return rows, ct, st, (1.0 / abs(ct) if rows else 1.0 / abs(st))
+
+    def _coord(self, rows, ct, st, s, k):
+        """matrix()'s expression for the ray coordinate q of detector offsets s at marching indices k (broadcast)."""
+        half = (self.N - 1) / 2.0
+        if rows:
+            y = half - k
+            return (s - y * st) / ct + half
+        x = k - half
+        return half - (s - x * ct) / st
+
+    def rows(self, ray_idx):
+        """CSR (len(ray_idx), N*N), float64: the rows of matrix() for the rays a * n_det + d, one angle's rays at a time, without
+        the other rows — the same expressions for q, floor, f, w and scale, hence the same bits (explicit zeros eliminated)."""
+        ray_idx = np.asarray(ray_idx, dtype=np.int64).reshape(-1)
+        N, nd = self.N, self.n_det
+        k = np.arange(N)
+        ri, ci, vv = [], [], []
+        aa, dd = np.divmod(ray_idx, nd)
+        for a in np.unique(aa):
+            sel = np.nonzero(aa == a)[0]
+            rows, ct, st, w = self._mode(a)
+            s = dd[sel] - (nd - 1) / 2.0
+            q = self._coord(rows, ct, st, s[:, None], k[None, :])
+            q0 = np.floor(q)
+            f = q - q0
+            for off, wt in ((0, 1.0 - f), (1, f)):
+                t = (q0 + off).astype(np.int64)
+                ok = (t >= 0) & (t < N)
+                lin = (k[None, :] * N + t) if rows else (t * N + k[None, :])
+                val = w * wt
+                val = val * self.scale
+                r = np.broadcast_to(sel[:, None], ok.shape)
+                ri.append(r[ok]); ci.append(lin[ok]); vv.append(val[ok])
+        cat = lambda parts, dt: np.concatenate(parts) if parts else np.zeros(0, dtype=dt)
+        R = sp.csr_matrix((cat(vv, np.float64), (cat(ri, np.int64), cat(ci, np.int64))), shape=(ray_idx.size, N * N))
+        R.eliminate_zeros()
+        return R
+
+    def cols(self, pix_idx):
+        """CSC (n_ang * n_det, len(pix_idx)), float64: the columns of matrix() for the pixels i * N + j.  Per pixel and angle the
+        detector nearest the pixel's inverse image, s* = x_j cos + y_i sin, is solved for; the candidates d0 - 2 .. d0 + 2 (a
+        ray's two taps are within one pixel of q and |dq/dd| >= 1, so d0 +- 1 would do) are evaluated with matrix()'s own
+        formula and the non-zeros kept."""
+        pix_idx = np.asarray(pix_idx, dtype=np.int64).reshape(-1)
+        N, nd = self.N, self.n_det
+        half = (N - 1) / 2.0
+        pi, pj = np.divmod(pix_idx, N)
+        ri, ci, vv = [], [], []
+        pcol = np.broadcast_to(np.arange(pix_idx.size)[:, None], (pix_idx.size, 5))
+        for a in range(len(self.angles)):
+            rows, ct, st, w = self._mode(a)
+            d0 = np.rint((pj - half) * ct + (half - pi) * st + (nd - 1) / 2.0).astype(np.int64)
+            d = d0[:, None] + np.arange(-2, 3)[None, :]
+            k, tap = (pi, pj) if rows else (pj, pi)
+            q = self._coord(rows, ct, st, d - (nd - 1) / 2.0, k[:, None])
+            q0 = np.floor(q)
+            f = q - q0
+            live = (d >= 0) & (d < nd)
+            for off, wt in ((0, 1.0 - f), (1, f)):
+                ok = live & ((q0 + off).astype(np.int64) == tap[:, None])
+                val = w * wt
+                val = val * self.scale
+                ri.append(a * nd + d[ok]); ci.append(pcol[ok]); vv.append(val[ok])
+        C = sp.csc_matrix((np.concatenate(vv), (np.concatenate(ri), np.concatenate(ci))), shape=(self.shape[0], pix_idx.size))
+        C.eliminate_zeros()
+        return C
+
+    def geometry(self, ray_idx):
+        """Per ray: the marching mode (0: rows, |cos| >= |sin|; 1: columns) and w = 1/|cos| or 1/|sin| (without `scale`)."""
+        a = np.asarray(ray_idx, dtype=np.int64).reshape(-1) // self.n_det
+        geo = [self._mode(k) for k in range(len(self.angles))]
+        mode = np.array([0 if g[0] else 1 for g in geo], dtype=np.int64)
+        w = np.array([g[3] for g in geo], dtype=np.float64)
+        return mode[a], w[a]
+
     def _fwd(self, x):
         return self.matrix() @ x
 

@@ -498,6 +498,19 @@ static int radon_create_impl(int N, int n_det, const double* angles, int nt, int
         c1m_d[(size_t)f * na + a] = c1p_d[(size_t)f * na + a] = (float)(pick / one);        // |pick| < 2^23: exact
       }
     }
+    // A handle that has the mirrored-pair adjoint takes it for a plain apply and k_radon_adj_tile for one that carries a rider: both must
+    // be ONE matrix.  k_radon_adj_quad weighs the four members of a quad with the quad's c1 (one packed FMA serves them all), so here the
+    // members take that value too — with their own, from the diffusion over the angles above, every neighbour weight of about half the
+    // angles differed between the two routes by one grid step (2048^2, two quads: up to 1.5 x 2^-24 w scale on ~450 pixels of a ray).
+    if (im->adjq_ok)
+      for (int f = 0; f < nt; ++f)
+        for (int k = 0; k < nq; ++k)
+          for (int m = 0; m < 4; ++m) {
+            const int am = quads[(size_t)f * nq + k].am[m];
+            if (am < 0) continue;
+            c1m_d[(size_t)f * na + am] = adjq_h[(size_t)f * nq + k].c1m;
+            c1p_d[(size_t)f * na + am] = adjq_h[(size_t)f * nq + k].c1p;
+          }
     for (int f = 0; f < nt; ++f) {
       int pos = 0;
       for (int pass = 0; pass < 2; ++pass) {

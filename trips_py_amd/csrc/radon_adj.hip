@@ -822,6 +822,18 @@ __global__ __launch_bounds__(256, 3) void k_radon_adj_quad(const uint4* __restri
           weigh(1, cb_y, cr);
         }
       }
+      // A batch of fewer than QB quads (the last one when nq % QB != 0) ends with its last quad's re-read of half 0 in flight, and nobody
+      // weighs it.  It has to land while ra[0] / rb[0] are still its registers: to the compiler they are free from the read's statement
+      // on, and unwaited the eight records land in whatever they hold by then — the addresses and sums of the pass below (2048^2 with
+      // two quads: ~100 pixels per apply that change from run to run, some of them table bits read as floats).
+      if (nql < QB) {
+        ring_wait();
+#pragma unroll
+        for (int k = 0; k < PX; ++k) {
+          ring_tie(ra[0][k]);
+          ring_tie(rb[0][k]);
+        }
+      }
     }
     // the sub-phase's sums meet the other one's in LDS: pixel (row, col) of tile set h, interpolated index col_k (h = 0) or its mirror
 #pragma unroll

@@ -21,7 +21,7 @@ constexpr int QD_MAXCH = 32;      // chunks of a band, at most
 constexpr int ADJ_T = 32;           // adjoint: tile edge (pixels) of the large-image instantiation; small images: 16 x 16, one pixel per thread
 // band-resident forward (k_radon_fwd_band)
 constexpr int BR_ROWS = 64, BR_NW = 16, BR_NT = 64 * BR_NW, BR_PAD = 4, BR_NMAX = 1024;
-// rows per band: 64 where 64 x (N + 8) floats fit (N <= 512), else 32 (N <= 1024: 132 KB)
+// rows per band: 64 where 64 x (N + 8) floats fit in 150 KB (N <= 592, i.e. the multiples of 64 up to 576), else 32 (N <= 1024: 132 KB)
 inline int br_rows(int N) { return (size_t)BR_ROWS * (N + 2 * BR_PAD) * 4 <= 150 * 1024 ? BR_ROWS : BR_ROWS / 2; }
 
 struct AngleParam {
