@@ -787,8 +787,8 @@ int trk::gemv_n_partials(const float* V, int64_t ld, int k, int64_t n, const dou
     *nblk = 0;
     return TRK_OK;
   }
-  // 8 workgroups per CU (tools/gemv_micro.py)
-  const int grid_n = (int)std::min<int64_t>((n + (int64_t)NT * 4 - 1) / ((int64_t)NT * 4), (int64_t)cu_count() * 8);
+  // 8 workgroups per CU (tools/gemv_micro.py); one workgroup for n = 0 (nothing to write, *sumsq = 0)
+  const int grid_n = (int)std::max<int64_t>(1, std::min<int64_t>((n + (int64_t)NT * 4 - 1) / ((int64_t)NT * 4), (int64_t)cu_count() * 8));
   if (sumsq)                                                     // one partial per workgroup of the grid actually launched
     if (int rc = scratch_doubles(s, (size_t)(grid_n > grid ? grid_n : grid), &part)) return rc;
   with_bools([&](auto HAS_BASE, auto SUMSQ, auto VEC) {
