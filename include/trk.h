@@ -624,6 +624,46 @@ int trk_cgls_iterate_fused(trk_op* A, int k_first, int n_iters, float* P, int64_
 int trk_finalize_batched(const double* partials, int nblocks, int nvals, int batches, double* out, int out_stride,
                          trk_stream stream);
 
+/* ---------------------------------------------------------------- MRNSD: steepest descent under x >= 0 --- */
+/* The modified residual norm steepest descent of Nagy and Strakos (IR Tools' IRmrnsd): min ||b - A x|| over x >= 0.  Vectors fp32,
+ * scalars and reductions fp64, no atomics.  With r = b - A x, g = -A^T r, s = -(x . g):
+ *   gamma = -sum g_i s_i ;  bound = min over {i : s_i < 0} of x_i / -s_i, +inf when no s_i is negative
+ *   iteration k: u = A s ; z = A^T u ; theta = gamma / ||u||^2 ; alpha = min(theta, bound), and alpha = 0 if ||u||^2 <= 0 or
+ *     gamma <= 0 (a broken-down state freezes) ; step = (float)alpha ;
+ *     x' = fmaxf(fmaf(step, s, x), 0) ; g' = fmaf(step, z, g) ; s' = -(x' * g') ; r' = fmaf(-step, u, r) ; gamma', bound' from them.
+ * Scalar block S (doubles):
+ *   S[0..2] = gamma_0, bound_0, ||r_0||^2
+ *   row k (1-based) at S + 8k = [||u_k||^2, alpha_k, gamma_k, bound_k, ||x_k||^2, ||step s||^2, ||x_k - x_true||^2, ||r_k||^2]
+ *   gamma_k, bound_k are the values iteration k LEAVES (what iteration k + 1 consumes); bounded step k: alpha_k < gamma_{k-1} / ||u_k||^2.
+ * A "gb buffer" holds block partials: gamma's at [0, gb_capacity), bound's at [gb_capacity, 2 gb_capacity).  A kernel never writes
+ * the gb buffer it reads (other blocks of the launch are still reading): the callers ping-pong two of them.
+ *
+ * trk_mrnsd_init: s = -(x0 . g), the gamma_0 / bound_0 partials into gb_out (*n_blocks of each: the block count of every later
+ *   update of the same n, m) and the finished S0[0..2] = gamma_0, bound_0, ||r||^2.  Two launches.
+ * trk_mrnsd_update: the vector work of one iteration in ONE launch.  gamma, bound, unorm are scalar sources (n = 1: finished; n > 1:
+ *   block partials, summed / minimised by one wave of every block, always in the same order).  x_new may be x; g, s, r are updated in
+ *   place.  The new gamma / bound partials go to gb_out; block 0 stores row[0] = ||u||^2, row[1] = alpha and, with publish_gb,
+ *   publish_gb[0..1] = the gamma and bound it consumed.  norm_partials: *n_blocks x 4 = ||x'||^2, ||step s||^2, ||x' - x_true||^2
+ *   (0 without x_true), ||r'||^2, summed for all iterations at once by trk_finalize_batched.
+ * trk_mrnsd_finish: out[0] = S(gamma), out[1] = min(bound) by one block — the bits the next update would publish.
+ * trk_mrnsd_iterate: iterations k_first .. k_first + n_iters - 1 enqueued by one call, nothing read back.  Iteration k reads GB's
+ *   half (k-1) & 1 and writes half k & 1 (GB: 4 gb_capacity doubles; trk_mrnsd_init writes half 0), publishes gamma_{k-1}, bound_{k-1}
+ *   into row k-1 (S[0..1] for k = 1) and writes iterate k to slot k-1 of X (keep_history) or (k-1) & 1.  *n_np_inout: the block count
+ *   trk_mrnsd_init returned.  NP: 4 * np_capacity_blocks * (iterations in all) doubles; iteration k's partials at NP + 4 n_np (k-1).
+ *   PU (may be NULL): pcap doubles; with it and an operator that leaves raw partials (trk_op_fused_caps) ||u||^2 stays block partials
+ *   and an iteration is three launches; else trk_op_apply finishes the sum into row k.  gamma_k, bound_k of the LAST iteration stay
+ *   partials in GB's half k & 1: trk_mrnsd_finish puts them into row k. */
+int trk_mrnsd_init(int64_t n, int64_t m, const float* x0, const float* g, const float* r, float* s, double* gb_out, int gb_capacity,
+                   double* S0, int* n_blocks, trk_stream stream);
+int trk_mrnsd_update(int64_t n, int64_t m, const double* gamma, int gamma_n, const double* bound, int bound_n, const double* unorm,
+                     int unorm_n, const float* x, float* x_new, float* g, float* s, const float* z, float* r, const float* u,
+                     const float* x_true, double* gb_out, int gb_capacity, double* row, double* publish_gb, double* norm_partials,
+                     int capacity_blocks, int* n_blocks, trk_stream stream);
+int trk_mrnsd_finish(const double* gamma, int gamma_n, const double* bound, int bound_n, double* out, trk_stream stream);
+int trk_mrnsd_iterate(trk_op* A, int k_first, int n_iters, float* g, float* s, float* z, float* r, float* u, float* X, int64_t x_ld,
+                      int keep_history, const float* x_prev, const float* x_true, double* S, double* GB, int gb_capacity, double* NP,
+                      int np_capacity_blocks, int* n_np_inout, double* PU, int pcap, trk_stream stream);
+
 /* ---------------------------------------------------------------- tall-skinny basis ops */
 /* h[j] = sum_i w2[i] * V[j][i] * r[i], j < k  (w2 may be NULL = 1).  One pass over V.
  * (V^T r of the (re)orthogonalisation: decompositions.py:90-94,216-218; GKS.py:86-88; MMGKS.py:119-120;

@@ -297,6 +297,55 @@ __device__ __forceinline__ double scalar_from_wave(const ScalarSrc s, int lane) 
   return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
 }
 
+// ------------------------------------------------------------------ minima (fp64), beside the sums
+// The identity is +inf.  A NaN wins: min_nan(a, b) is NaN when either operand is, so a NaN among the values reaches the result instead
+// of being dropped by a comparison that is false.  Apart from that a minimum is exact and does not depend on the order it is taken
+// in: every tree gives the same bits.
+// PRECONDITION of wave_min_all, block_min and scalar_min_from_wave, as of wave_sum and scalar_from_wave: a FULL wave — all 64 lanes
+// active and converged at the call (the cross-lane reads return 0 for an inactive lane, which would win every minimum of positive
+// values).  `if (threadIdx.x < 64)` of a workgroup of whole waves is such a place; a data-dependent branch is not.
+__device__ __forceinline__ double min_nan(double a, double b) { return (b < a || b != b) ? b : a; }
+
+__device__ __forceinline__ double wave_min_all(double v) {   // the minimum in every lane
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) v = min_nan(v, __shfl_xor(v, off, 64));
+  return v;
+}
+
+// Minimum over a block of NT threads (NT multiple of 64; every thread calls).  `lds` holds NT/64 doubles.  Result valid in thread 0.
+template <int NT>
+__device__ __forceinline__ double block_min(double v, double* lds) {
+  constexpr int NW = NT / 64;
+  v = wave_min_all(v);
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  __syncthreads();  // protect lds reuse between consecutive calls
+  if (lane == 0) lds[wid] = v;
+  __syncthreads();
+  double t = __builtin_inf();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int w = 0; w < NW; ++w) t = min_nan(t, lds[w]);
+  }
+  return t;
+}
+
+// scalar_from_wave for a minimum: n == 0: +inf ; n == 1: *p ; n > 1: the minimum of n block partials.  Called by ONE full wave;
+// returns the value in every lane.
+__device__ __forceinline__ double scalar_min_from_wave(const ScalarSrc s, int lane) {
+  if (s.n == 0) return __builtin_inf();
+  if (s.n == 1) return *s.p;
+  double a0 = __builtin_inf(), a1 = a0, a2 = a0, a3 = a0;
+  int i = lane;
+  for (; i + 192 < s.n; i += 256) {      // four loads of a round in flight together
+    a0 = min_nan(a0, s.p[i]);
+    a1 = min_nan(a1, s.p[i + 64]);
+    a2 = min_nan(a2, s.p[i + 128]);
+    a3 = min_nan(a3, s.p[i + 192]);
+  }
+  for (; i < s.n; i += 64) a0 = min_nan(a0, s.p[i]);
+  return wave_min_all(min_nan(min_nan(a0, a1), min_nan(a2, a3)));
+}
+
 // the coefficient of trk_op_apply_ratio: c = sign * (float)(S(num) / S(den)); on_z = 0: out = c Op(x) + z, 1: out = Op(x) + c z;
 // workgroup 0 stores the finished S(den) (pub_den != 0) or S(num) to *pub (may be NULL)
 struct RatioCoef {

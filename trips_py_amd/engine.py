@@ -674,6 +674,42 @@ class HipEngine:
         _lib.check(rc, "trk_cgls_iterate_sharded")
         return n.value, ng.value
 
+    # ------------------------------------------------------------------ MRNSD (mrnsd.hip; the S / gb layout: include/trk.h)
+    def mrnsd_init(self, x0, g, r, s, gb_out, gb_capacity, S0):
+        """s = -(x0 . g), the gamma_0 / bound_0 block partials into gb_out, S0[0..2] = gamma_0, bound_0, ||r||^2; returns the block count."""
+        n = ctypes.c_int(0)
+        rc = self.lib.trk_mrnsd_init(x0.numel(), r.numel(), x0.data_ptr(), g.data_ptr(), r.data_ptr(), s.data_ptr(), _ptr(gb_out),
+                                     int(gb_capacity), _ptr(S0), ctypes.byref(n), self.stream())
+        _lib.check(rc, "trk_mrnsd_init")
+        return n.value
+
+    def mrnsd_update(self, gamma, gamma_n, bound, bound_n, unorm, unorm_n, x, x_new, g, s, z, r, u, x_true, gb_out, gb_capacity, row,
+                     pub_gb, partials, capacity):
+        """The vector work of one MRNSD iteration in one launch; returns the block count."""
+        n = ctypes.c_int(0)
+        rc = self.lib.trk_mrnsd_update(x.numel(), r.numel(), _ptr(gamma), int(gamma_n), _ptr(bound), int(bound_n), _ptr(unorm),
+                                       int(unorm_n), x.data_ptr(), x_new.data_ptr(), g.data_ptr(), s.data_ptr(), z.data_ptr(),
+                                       r.data_ptr(), u.data_ptr(), None if x_true is None else x_true.data_ptr(), _ptr(gb_out),
+                                       int(gb_capacity), _ptr(row), _ptr(pub_gb), _ptr(partials), int(capacity), ctypes.byref(n),
+                                       self.stream())
+        _lib.check(rc, "trk_mrnsd_update")
+        return n.value
+
+    def mrnsd_finish(self, gamma, gamma_n, bound, bound_n, out):
+        rc = self.lib.trk_mrnsd_finish(_ptr(gamma), int(gamma_n), _ptr(bound), int(bound_n), _ptr(out), self.stream())
+        _lib.check(rc, "trk_mrnsd_finish")
+
+    def mrnsd_iterate(self, handle, k_first, n_iters, g, s, z, r, u, X, keep, x_prev, x_true, S, GB, gb_capacity, NP, np_cap, n_np,
+                      PU=None, pcap=0):
+        """n_iters MRNSD iterations in one library call; returns the partial-block count."""
+        c = ctypes.c_int(int(n_np))
+        rc = self.lib.trk_mrnsd_iterate(handle, int(k_first), int(n_iters), g.data_ptr(), s.data_ptr(), z.data_ptr(), r.data_ptr(),
+                                        u.data_ptr(), X.data_ptr(), X.stride(0), int(bool(keep)), x_prev.data_ptr(),
+                                        None if x_true is None else x_true.data_ptr(), _ptr(S), _ptr(GB), int(gb_capacity), _ptr(NP),
+                                        int(np_cap), ctypes.byref(c), _ptr(PU), int(pcap), self.stream())
+        _lib.check(rc, "trk_mrnsd_iterate")
+        return c.value
+
     def finalize_batched(self, partials, nblocks, nvals, batches, out, out_stride):
         rc = self.lib.trk_finalize_batched(_ptr(partials), int(nblocks), int(nvals), int(batches), _ptr(out), int(out_stride),
                                            self.stream())

@@ -1,6 +1,7 @@
 """Krylov / projection solvers and the dense direct solvers (tSVD, tGSVD, Tikhonov) with the reference's signatures
 (trips/solvers/*.py), running on the HIP engine."""
 from .CGLS import CGLS, CGLSRun, CGLSRunFused, CGLSRunSharded  # noqa: F401
+from .MRNSD import MRNSD, MRNSDRun  # noqa: F401
 from .Hybrid_LSQR import Hybrid_LSQR  # noqa: F401
 from .Hybrid_GMRES import Hybrid_GMRES  # noqa: F401
 from .GKS import GKS  # noqa: F401
