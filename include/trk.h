@@ -664,6 +664,57 @@ int trk_mrnsd_iterate(trk_op* A, int k_first, int n_iters, float* g, float* s, f
                       int keep_history, const float* x_prev, const float* x_true, double* S, double* GB, int gb_capacity, double* NP,
                       int np_capacity_blocks, int* n_np_inout, double* PU, int pcap, trk_stream stream);
 
+/* ---------------------------------------------------------------- PDHG: TV / l1 under box constraints --- */
+/* The primal-dual hybrid gradient iteration (Chambolle and Pock 2011, algorithm 1, theta = 1) for
+ *   min_x  1/2 ||A x - b||^2 + lam ||L x||_1   subject to  lo <= x <= hi.
+ * K = [A; L], duals p (rows of A) and q (rows of L), p_0 = q_0 = 0, x_0 inside the box, xbar_0 = x_0.  One iteration:
+ *   w = A xbar ;  p' = (p + sigma (w - b)) / (1 + sigma)
+ *   u = L xbar ;  q' = clip(q + sigma u, -lam, lam)
+ *   z = A^T p' ;  v = L^T q' ;  x' = clip(x - tau (z + v), lo, hi) ;  xbar' = 2 x' - x
+ * Vectors fp32; the host scalars are rounded once: sf = (float)sigma, tf = (float)tau, lf = (float)lam, cf = (float)(1 / (1 + sigma)),
+ * lof = (float)lo, hif = (float)hi (-inf / +inf allowed).  The fp32 operations, in this order, every multiply-add an fmaf, nothing
+ * else contracted:
+ *   dual p:   e = w - b ;  p' = fmaf(sf, e, p) * cf
+ *   dual q:   q' = fminf(fmaxf(fmaf(sf, u, q), -lf), lf)
+ *   primal:   g = z + v ;  x' = fminf(fmaxf(fmaf(-tf, g, x), lof), hif) ;  xbar' = fmaf(2, x', -x) ;  d = x' - x
+ *   2-D first differences (fused forms): u is xbar[i][j] - xbar[i][j+1], then xbar[i][j] - xbar[i+1][j] (the rows of trk_deriv2d_create) ;
+ *     v is gathered as 0, + H[i][j], - H[i][j-1], + V[i][j], - V[i-1][j], absent terms skipped (the operator's own transpose).
+ * Sums: fp64 block partials in ROWS OF 8 — block j of a kernel writes its slots of partials[8 j .. 8 j + 7] and nothing else, so the
+ * kernels of one iteration share one zeroed block of 8 * capacity_blocks doubles and trk_finalize_batched(NP, capacity, 8, iterations,
+ * S + 8, 8) leaves row k (1-based) at S + 8k:
+ *   [ ||w - b||^2, sum |u|, ||p' - p||^2, ||q' - q||^2, ||x'||^2, ||d||^2, ||x' - x_true||^2 (0 without x_true),
+ *     the number of entries of x' equal to lof or hif ]
+ * Slots 0 and 1 are the residual and the regulariser AT THE POINT THE ITERATION APPLIES A AND L TO, xbar_{k-1} = 2 x_{k-1} - x_{k-2},
+ * not at x_k: they cost no product of their own.  (p' - p, q' - q and x' - x_true are formed in fp64 from the fp32 values.)
+ *
+ * trk_pdhg_dual_p (slots 0, 2; p in place), trk_pdhg_dual_q (slots 1, 3; q in place; any L), trk_pdhg_primal (slots 4..7; v = NULL:
+ *   no regulariser term; x_new may be x; xbar may alias nothing): streaming kernels, 16-byte accesses where every operand is 16-byte
+ *   aligned.  *n_blocks: the blocks that wrote.
+ * trk_pdhg_tv_dual, trk_pdhg_tv_primal: the fused forms for a handle from trk_deriv2d_create — the dual forms the differences of
+ *   xbar in registers (xbar read, q read and written), the primal gathers L^T q itself (x, z, q read; x', xbar' written): nothing of
+ *   the length of L xbar or L^T q touches memory.  The same entries as the streaming kernels: the same bits in q, x', xbar'.  Any other
+ *   handle: TRK_EUNSUPPORTED.  trk_pdhg_fused_caps: *can = 1 where a handle takes them.
+ * trk_pdhg_blocks: the largest block count of an iteration's kernels (L_fused: the handle of the fused forms, or NULL).
+ * trk_pdhg_iterate: iterations k_first .. k_first + n_iters - 1 enqueued by one call, nothing read back.  Iteration k takes x_{k-1}
+ *   from x_prev (k = k_first) or the slot it wrote, writes iterate k to slot k-1 of X (keep_history) or (k-1) & 1, and its partials
+ *   to NP + 8 np_capacity_blocks (k-1) (zeroed by the caller).  With `fused` u and v are unused (may be NULL): five launches. */
+int trk_pdhg_blocks(int64_t m, int64_t n, int64_t rows, const trk_op* L_fused, int* blocks);
+int trk_pdhg_dual_p(int64_t m, double sigma, const float* w, const float* b, float* p, double* partials, int capacity_blocks,
+                    int* n_blocks, trk_stream stream);
+int trk_pdhg_dual_q(int64_t rows, double sigma, double lam, const float* u, float* q, double* partials, int capacity_blocks,
+                    int* n_blocks, trk_stream stream);
+int trk_pdhg_primal(int64_t n, double tau, double lo, double hi, const float* x, const float* z, const float* v, float* x_new,
+                    float* xbar, const float* x_true, double* partials, int capacity_blocks, int* n_blocks, trk_stream stream);
+int trk_pdhg_fused_caps(const trk_op* L, int* can);
+int trk_pdhg_tv_dual(trk_op* L, double sigma, double lam, const float* xbar, float* q, double* partials, int capacity_blocks,
+                     int* n_blocks, trk_stream stream);
+int trk_pdhg_tv_primal(trk_op* L, double tau, double lo, double hi, const float* x, const float* z, const float* q, float* x_new,
+                       float* xbar, const float* x_true, double* partials, int capacity_blocks, int* n_blocks, trk_stream stream);
+int trk_pdhg_iterate(trk_op* A, trk_op* L, int k_first, int n_iters, double sigma, double tau, double lam, double lo, double hi,
+                     int fused, const float* b, float* p, float* q, float* w, float* u, float* z, float* v, float* X, int64_t x_ld,
+                     int keep_history, const float* x_prev, float* xbar, const float* x_true, double* NP, int np_capacity_blocks,
+                     trk_stream stream);
+
 /* ---------------------------------------------------------------- tall-skinny basis ops */
 /* h[j] = sum_i w2[i] * V[j][i] * r[i], j < k  (w2 may be NULL = 1).  One pass over V.
  * (V^T r of the (re)orthogonalisation: decompositions.py:90-94,216-218; GKS.py:86-88; MMGKS.py:119-120;

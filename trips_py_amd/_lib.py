@@ -16,7 +16,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB_PATH = os.path.join(CSRC, "libtrk.so")
-SOURCES = ["core.hip", "vecops.hip", "blur2d.hip", "blur_tile.hip", "gemv.hip", "wgram.hip", "tvops.hip", "radon2d.hip", "radon_fwd.hip", "radon_adj.hip", "spmv.hip", "framelet2d.hip", "fanbeam2d.hip", "projected.hip", "host_regparam.hip", "host_worker.hip", "hybrid_host.hip", "cgls_update.hip", "cgls_loop.hip", "mrnsd.hip", "comm.hip", "cgls_tiled.hip", "cgls_sharded.hip", "ref64.hip", "dense_svd.hip"]
+SOURCES = ["core.hip", "vecops.hip", "blur2d.hip", "blur_tile.hip", "gemv.hip", "wgram.hip", "tvops.hip", "radon2d.hip", "radon_fwd.hip", "radon_adj.hip", "spmv.hip", "framelet2d.hip", "fanbeam2d.hip", "projected.hip", "host_regparam.hip", "host_worker.hip", "hybrid_host.hip", "cgls_update.hip", "cgls_loop.hip", "mrnsd.hip", "pdhg.hip", "comm.hip", "cgls_tiled.hip", "cgls_sharded.hip", "ref64.hip", "dense_svd.hip"]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-I" + INCLUDE, "-I" + CSRC]
 
 
@@ -261,6 +261,17 @@ SIGNATURES = {
     "trk_mrnsd_finish": (c_int, [c_f64p, c_int, c_f64p, c_int, c_f64p, c_stream]),
     "trk_mrnsd_iterate": (c_int, [c_op, c_int, c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_i64, c_int, c_f32p, c_f32p,
                                   c_f64p, c_f64p, c_int, c_f64p, c_int, ctypes.POINTER(c_int), c_f64p, c_int, c_stream]),
+    "trk_pdhg_blocks": (c_int, [c_i64, c_i64, c_i64, c_op, ctypes.POINTER(c_int)]),
+    "trk_pdhg_dual_p": (c_int, [c_i64, c_dbl, c_f32p, c_f32p, c_f32p, c_f64p, c_int, ctypes.POINTER(c_int), c_stream]),
+    "trk_pdhg_dual_q": (c_int, [c_i64, c_dbl, c_dbl, c_f32p, c_f32p, c_f64p, c_int, ctypes.POINTER(c_int), c_stream]),
+    "trk_pdhg_primal": (c_int, [c_i64, c_dbl, c_dbl, c_dbl, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f64p, c_int,
+                                ctypes.POINTER(c_int), c_stream]),
+    "trk_pdhg_fused_caps": (c_int, [c_op, ctypes.POINTER(c_int)]),
+    "trk_pdhg_tv_dual": (c_int, [c_op, c_dbl, c_dbl, c_f32p, c_f32p, c_f64p, c_int, ctypes.POINTER(c_int), c_stream]),
+    "trk_pdhg_tv_primal": (c_int, [c_op, c_dbl, c_dbl, c_dbl, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f64p, c_int,
+                                   ctypes.POINTER(c_int), c_stream]),
+    "trk_pdhg_iterate": (c_int, [c_op, c_op, c_int, c_int, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl, c_int, c_f32p, c_f32p, c_f32p, c_f32p,
+                                 c_f32p, c_f32p, c_f32p, c_f32p, c_i64, c_int, c_f32p, c_f32p, c_f32p, c_f64p, c_int, c_stream]),
     "trk_gemv_t": (c_int, [c_f32p, c_i64, c_int, c_i64, c_f32p, c_f32p, c_f64p, c_stream]),
     "trk_gemv_t_x": (c_int, [c_f32p, c_i64, c_int, c_i64, c_f32p, c_f32p, c_f64p, c_f64p, c_stream]),
     "trk_gemv_t2": (c_int, [c_f32p, c_i64, c_int, c_i64, c_f32p, c_f32p, c_f64p, c_stream]),

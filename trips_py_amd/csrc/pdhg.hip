@@ -1,0 +1,233 @@
+// pdhg.hip — the primal-dual hybrid gradient iteration (Chambolle and Pock 2011, algorithm 1, theta = 1) for
+//   min_x  1/2 ||A x - b||^2 + lam ||L x||_1   subject to  lo <= x <= hi
+// with K = [A; L], duals p (rows of A) and q (rows of L), and the extrapolated point xbar = 2 x_k - x_{k-1}:
+//   w = A xbar ;  p' = (p + sig (w - b)) / (1 + sig)
+//   u = L xbar ;  q' = clip(q + sig u, -lam, lam)
+//   z = A^T p' ;  v = L^T q' ;  x' = clip(x - tau (z + v), lo, hi) ;  xbar' = 2 x' - x
+// sig, tau, lam, lo, hi are host constants: nothing is read back inside the loop and trk_pdhg_iterate enqueues a whole solve.
+// The three streaming kernels are here; the fused forms for the 2-D first differences (no vector of the length of L xbar or L^T q
+// in memory) are in tvops.hip and share one entry (pdhg_internal.h).  Vectors fp32, sums fp64 block partials, no atomics: every
+// result is reproducible from run to run.  docs/kernels/pdhg.md: the byte count, why xbar is stored.
+#include "vec_internal.h"
+#include "pdhg_internal.h"
+
+using namespace trk;
+
+namespace {
+
+// A kernel writes ITS slots of ITS blocks' rows of 8 partials (include/trk.h) and leaves the rest as it finds them: the caller zeroes.
+// p in place (an entry is read and then written by the same thread): no __restrict__ on it.
+template <bool VEC>
+__global__ __launch_bounds__(NT) void k_pdhg_dual_p(int64_t m, float sig, float c, const float* __restrict__ w,
+                                                    const float* __restrict__ b, float* p, double* __restrict__ partials) {
+  __shared__ double lds[NT / 64];
+  double s0 = 0.0, s2 = 0.0;
+  const int64_t tid = (int64_t)blockIdx.x * NT + threadIdx.x, nth = (int64_t)gridDim.x * NT;
+  int64_t tail = 0;
+  if (VEC) {
+    const int64_t m4 = m >> 2;
+    tail = m4 << 2;
+    for (int64_t i = tid; i < m4; i += nth) {
+      const float4 wv = ld4(w, i), bv = ld4(b, i);
+      float4 pv = ld4(p, i);
+      pv.x = pdhg_p_entry(sig, c, wv.x, bv.x, pv.x, s0, s2);
+      pv.y = pdhg_p_entry(sig, c, wv.y, bv.y, pv.y, s0, s2);
+      pv.z = pdhg_p_entry(sig, c, wv.z, bv.z, pv.z, s0, s2);
+      pv.w = pdhg_p_entry(sig, c, wv.w, bv.w, pv.w, s0, s2);
+      st4(p, i, pv);
+    }
+  }
+  for (int64_t i = tail + tid; i < m; i += nth) p[i] = pdhg_p_entry(sig, c, w[i], b[i], p[i], s0, s2);
+  s0 = block_sum<NT>(s0, lds);
+  s2 = block_sum<NT>(s2, lds);
+  if (threadIdx.x == 0) {
+    partials[blockIdx.x * 8 + 0] = s0;
+    partials[blockIdx.x * 8 + 2] = s2;
+  }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(NT) void k_pdhg_dual_q(int64_t rows, float sig, float lam, const float* __restrict__ u, float* q,
+                                                    double* __restrict__ partials) {
+  __shared__ double lds[NT / 64];
+  double s1 = 0.0, s3 = 0.0;
+  const int64_t tid = (int64_t)blockIdx.x * NT + threadIdx.x, nth = (int64_t)gridDim.x * NT;
+  int64_t tail = 0;
+  if (VEC) {
+    const int64_t r4 = rows >> 2;
+    tail = r4 << 2;
+    for (int64_t i = tid; i < r4; i += nth) {
+      const float4 uv = ld4(u, i);
+      float4 qv = ld4(q, i);
+      qv.x = pdhg_q_entry(sig, lam, uv.x, qv.x, s1, s3);
+      qv.y = pdhg_q_entry(sig, lam, uv.y, qv.y, s1, s3);
+      qv.z = pdhg_q_entry(sig, lam, uv.z, qv.z, s1, s3);
+      qv.w = pdhg_q_entry(sig, lam, uv.w, qv.w, s1, s3);
+      st4(q, i, qv);
+    }
+  }
+  for (int64_t i = tail + tid; i < rows; i += nth) q[i] = pdhg_q_entry(sig, lam, u[i], q[i], s1, s3);
+  s1 = block_sum<NT>(s1, lds);
+  s3 = block_sum<NT>(s3, lds);
+  if (threadIdx.x == 0) {
+    partials[blockIdx.x * 8 + 1] = s1;
+    partials[blockIdx.x * 8 + 3] = s3;
+  }
+}
+
+// x_new may be x (read, then written by the same thread): no __restrict__ on the two.  HAS_V = false: no regulariser term, g = z.
+template <bool HAS_V, bool HAS_XT, bool VEC>
+__global__ __launch_bounds__(NT) void k_pdhg_primal(int64_t n, float tau, float lo, float hi, const float* x, const float* __restrict__ z,
+                                                    const float* __restrict__ v, float* x_new, float* __restrict__ xbar,
+                                                    const float* __restrict__ x_true, double* __restrict__ partials) {
+  __shared__ double lds[NT / 64];
+  double s4 = 0.0, s5 = 0.0, s6 = 0.0, s7 = 0.0;
+  const int64_t tid = (int64_t)blockIdx.x * NT + threadIdx.x, nth = (int64_t)gridDim.x * NT;
+  int64_t tail = 0;
+  if (VEC) {
+    const int64_t n4 = n >> 2;
+    tail = n4 << 2;
+    for (int64_t i = tid; i < n4; i += nth) {
+      const float4 xv = ld4(x, i), zv = ld4(z, i);
+      const float4 vv = HAS_V ? ld4(v, i) : make_float4(0.f, 0.f, 0.f, 0.f);
+      const float4 tv = HAS_XT ? ld4(x_true, i) : make_float4(0.f, 0.f, 0.f, 0.f);
+      float4 xn, xb;
+      pdhg_x_entry<HAS_XT>(tau, lo, hi, xv.x, HAS_V ? zv.x + vv.x : zv.x, tv.x, xn.x, xb.x, s4, s5, s6, s7);
+      pdhg_x_entry<HAS_XT>(tau, lo, hi, xv.y, HAS_V ? zv.y + vv.y : zv.y, tv.y, xn.y, xb.y, s4, s5, s6, s7);
+      pdhg_x_entry<HAS_XT>(tau, lo, hi, xv.z, HAS_V ? zv.z + vv.z : zv.z, tv.z, xn.z, xb.z, s4, s5, s6, s7);
+      pdhg_x_entry<HAS_XT>(tau, lo, hi, xv.w, HAS_V ? zv.w + vv.w : zv.w, tv.w, xn.w, xb.w, s4, s5, s6, s7);
+      st4(x_new, i, xn);
+      st4(xbar, i, xb);
+    }
+  }
+  for (int64_t i = tail + tid; i < n; i += nth) {
+    float xn, xb;
+    pdhg_x_entry<HAS_XT>(tau, lo, hi, x[i], HAS_V ? z[i] + v[i] : z[i], HAS_XT ? x_true[i] : 0.f, xn, xb, s4, s5, s6, s7);
+    x_new[i] = xn;
+    xbar[i] = xb;
+  }
+  s4 = block_sum<NT>(s4, lds);
+  s5 = block_sum<NT>(s5, lds);
+  if (HAS_XT) s6 = block_sum<NT>(s6, lds);
+  s7 = block_sum<NT>(s7, lds);
+  if (threadIdx.x == 0) {
+    partials[blockIdx.x * 8 + 4] = s4;
+    partials[blockIdx.x * 8 + 5] = s5;
+    partials[blockIdx.x * 8 + 6] = HAS_XT ? s6 : 0.0;
+    partials[blockIdx.x * 8 + 7] = s7;
+  }
+}
+
+inline bool finite_pos(double v) { return v > 0.0 && v < __builtin_inf(); }
+
+}  // namespace
+
+// ======================================================================================= C ABI
+extern "C" {
+
+int trk_pdhg_blocks(int64_t m, int64_t n, int64_t rows, const trk_op* L_fused, int* blocks) {
+  TRK_REQUIRE(blocks && m >= 1 && n >= 1 && rows >= 1, "trk_pdhg_blocks: need m, n, rows >= 1");
+  int g = stream_grid(m > n ? (m > rows ? m : rows) : (n > rows ? n : rows));
+  if (L_fused) {
+    const int t = pdhg_tv_blocks(L_fused);
+    if (t == 0) return fail(TRK_EUNSUPPORTED, "trk_pdhg_blocks: the fused forms take a handle from trk_deriv2d_create only");
+    if (t > g) g = t;
+  }
+  *blocks = g;
+  return TRK_OK;
+}
+
+int trk_pdhg_dual_p(int64_t m, double sigma, const float* w, const float* b, float* p, double* partials, int capacity_blocks,
+                    int* n_blocks, trk_stream st) {
+  TRK_REQUIRE(w && b && p && partials && n_blocks, "trk_pdhg_dual_p: NULL argument");
+  TRK_REQUIRE(m >= 1, "trk_pdhg_dual_p: need m >= 1");
+  TRK_REQUIRE(finite_pos(sigma), "trk_pdhg_dual_p: sigma must be finite and > 0");
+  TRK_REQUIRE(p != w && p != b, "trk_pdhg_dual_p: p must not alias w or b");
+  const int grid = stream_grid(m);
+  TRK_REQUIRE(grid <= capacity_blocks, "trk_pdhg_dual_p: partial buffer too small (%d blocks needed)", grid);
+  *n_blocks = grid;
+  with_bools([&](auto VEC) {
+    hipLaunchKernelGGL((k_pdhg_dual_p<VEC>), dim3(grid), dim3(NT), 0, (hipStream_t)st, m, (float)sigma, (float)(1.0 / (1.0 + sigma)), w, b,
+                       p, partials);
+  }, aligned16(w) && aligned16(b) && aligned16(p));
+  TRK_LAUNCH_CHECK();
+  return TRK_OK;
+}
+
+int trk_pdhg_dual_q(int64_t rows, double sigma, double lam, const float* u, float* q, double* partials, int capacity_blocks,
+                    int* n_blocks, trk_stream st) {
+  TRK_REQUIRE(u && q && partials && n_blocks, "trk_pdhg_dual_q: NULL argument");
+  TRK_REQUIRE(rows >= 1, "trk_pdhg_dual_q: need rows >= 1");
+  TRK_REQUIRE(finite_pos(sigma), "trk_pdhg_dual_q: sigma must be finite and > 0");
+  TRK_REQUIRE(lam >= 0.0 && lam < __builtin_inf(), "trk_pdhg_dual_q: lam must be finite and >= 0");
+  TRK_REQUIRE(q != u, "trk_pdhg_dual_q: q must not alias u");
+  const int grid = stream_grid(rows);
+  TRK_REQUIRE(grid <= capacity_blocks, "trk_pdhg_dual_q: partial buffer too small (%d blocks needed)", grid);
+  *n_blocks = grid;
+  with_bools([&](auto VEC) {
+    hipLaunchKernelGGL((k_pdhg_dual_q<VEC>), dim3(grid), dim3(NT), 0, (hipStream_t)st, rows, (float)sigma, (float)lam, u, q, partials);
+  }, aligned16(u) && aligned16(q));
+  TRK_LAUNCH_CHECK();
+  return TRK_OK;
+}
+
+int trk_pdhg_primal(int64_t n, double tau, double lo, double hi, const float* x, const float* z, const float* v, float* x_new,
+                    float* xbar, const float* x_true, double* partials, int capacity_blocks, int* n_blocks, trk_stream st) {
+  TRK_REQUIRE(x && z && x_new && xbar && partials && n_blocks, "trk_pdhg_primal: NULL argument");
+  TRK_REQUIRE(n >= 1, "trk_pdhg_primal: need n >= 1");
+  TRK_REQUIRE(finite_pos(tau), "trk_pdhg_primal: tau must be finite and > 0");
+  TRK_REQUIRE(lo <= hi, "trk_pdhg_primal: need lo <= hi (either may be infinite)");
+  TRK_REQUIRE(xbar != x && xbar != x_new && xbar != z && xbar != v && xbar != x_true,
+              "trk_pdhg_primal: xbar must not alias another operand");
+  TRK_REQUIRE(x_new != z && x_new != v && x_new != x_true, "trk_pdhg_primal: x_new may alias x only");
+  const int grid = stream_grid(n);
+  TRK_REQUIRE(grid <= capacity_blocks, "trk_pdhg_primal: partial buffer too small (%d blocks needed)", grid);
+  *n_blocks = grid;
+  const bool vec = aligned16(x) && aligned16(z) && aligned16(x_new) && aligned16(xbar) && (!v || aligned16(v)) &&
+                   (!x_true || aligned16(x_true));
+  with_bools([&](auto HAS_V, auto HAS_XT, auto VEC) {
+    hipLaunchKernelGGL((k_pdhg_primal<HAS_V, HAS_XT, VEC>), dim3(grid), dim3(NT), 0, (hipStream_t)st, n, (float)tau, (float)lo, (float)hi,
+                       x, z, v, x_new, xbar, x_true, partials);
+  }, v != nullptr, x_true != nullptr, vec);
+  TRK_LAUNCH_CHECK();
+  return TRK_OK;
+}
+
+int trk_pdhg_iterate(trk_op* A, trk_op* L, int k_first, int n_iters, double sigma, double tau, double lam, double lo, double hi,
+                     int fused, const float* b, float* p, float* q, float* w, float* u, float* z, float* v, float* X, int64_t x_ld,
+                     int keep_history, const float* x_prev, float* xbar, const float* x_true, double* NP, int np_capacity_blocks,
+                     trk_stream stream) {
+  TRK_REQUIRE(A && L && b && p && q && w && z && X && x_prev && xbar && NP, "trk_pdhg_iterate: NULL argument");
+  TRK_REQUIRE(fused || (u && v), "trk_pdhg_iterate: the generic path needs u and v");
+  TRK_REQUIRE(k_first >= 1 && n_iters >= 0, "trk_pdhg_iterate: need k_first >= 1, n_iters >= 0");
+  TRK_REQUIRE(L->cols == A->cols, "trk_pdhg_iterate: A and L must have the same number of columns");
+  const int64_t m = A->rows, n = A->cols, rows = L->rows;
+  int need = 0;
+  if (int rc = trk_pdhg_blocks(m, n, rows, fused ? L : nullptr, &need)) return rc;
+  TRK_REQUIRE(need <= np_capacity_blocks, "trk_pdhg_iterate: partial buffer too small (%d blocks needed)", need);
+  for (int k = k_first; k < k_first + n_iters; ++k) {
+    double* part = NP + 8 * (int64_t)np_capacity_blocks * (k - 1);
+    float* x_new = X + (int64_t)(keep_history ? (k - 1) : ((k - 1) & 1)) * x_ld;
+    int nb = 0, rc;
+    if ((rc = trk_op_apply(A, 0, xbar, 0, w, 0, 1, nullptr, stream))) return rc;                       // w = A xbar
+    if ((rc = trk_pdhg_dual_p(m, sigma, w, b, p, part, np_capacity_blocks, &nb, stream))) return rc;
+    if (fused) {
+      if ((rc = trk_pdhg_tv_dual(L, sigma, lam, xbar, q, part, np_capacity_blocks, &nb, stream))) return rc;
+    } else {
+      if ((rc = trk_op_apply(L, 0, xbar, 0, u, 0, 1, nullptr, stream))) return rc;                     // u = L xbar
+      if ((rc = trk_pdhg_dual_q(rows, sigma, lam, u, q, part, np_capacity_blocks, &nb, stream))) return rc;
+    }
+    if ((rc = trk_op_apply(A, 1, p, 0, z, 0, 1, nullptr, stream))) return rc;                          // z = A^T p'
+    if (fused) {
+      rc = trk_pdhg_tv_primal(L, tau, lo, hi, x_prev, z, q, x_new, xbar, x_true, part, np_capacity_blocks, &nb, stream);
+    } else {
+      if ((rc = trk_op_apply(L, 1, q, 0, v, 0, 1, nullptr, stream))) return rc;                        // v = L^T q'
+      rc = trk_pdhg_primal(n, tau, lo, hi, x_prev, z, v, x_new, xbar, x_true, part, np_capacity_blocks, &nb, stream);
+    }
+    if (rc) return rc;
+    x_prev = x_new;
+  }
+  return TRK_OK;
+}
+
+}  // extern "C"

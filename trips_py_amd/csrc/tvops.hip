@@ -11,6 +11,7 @@
 // For a time-sharded dynamic problem each rank owns whole frames; the temporal rows need the first frame of the next
 // rank (forward) and the last temporal block of the previous rank (transpose): trk_spacetime_set_halo.
 #include "trk_internal.h"
+#include "pdhg_internal.h"
 
 using namespace trk;
 
@@ -314,6 +315,113 @@ __global__ __launch_bounds__(NT) void k_time_fwd(const float* __restrict__ x, fl
   }
 }
 
+// Fused forms for PDHG (pdhg.hip; the entries: pdhg_internal.h), nothing of the length of L2 xbar or L2^T q touches memory:
+//   k_pdhg_tv_dual:    q' = clip(q + sig L2 xbar, -lam, lam), the differences formed in registers as k_d2_fwd forms them
+//                      (xbar read: 4n; q read and written: 8n + 8n); partials 1 (sum |L2 xbar|) and 3 (||q' - q||^2) of the block's row
+//   k_pdhg_tv_primal:  x' = clip(x - tau (z + L2^T q), lo, hi), xbar' = 2 x' - x, L2^T q gathered in the order of k_d2_adj
+//                      (x, z, q read: 16n; x', xbar' written: 8n); partials 4 to 7
+// One thread per image column over batches of RB rows, as the stencils above; every thread stays to the block sums.
+__global__ __launch_bounds__(NT) void k_pdhg_tv_dual(const float* __restrict__ xbar, float* q, int N, float sig, float lam,
+                                                     double* __restrict__ partials) {
+  __shared__ double red[NT / 64];
+  float* qh = q;
+  float* qv = q + (int64_t)N * (N - 1);
+  const int j = blockIdx.x * NT + threadIdx.x;
+  double s1 = 0.0, s3 = 0.0;
+  if (j < N) {
+    const bool hr = j < N - 1;
+    for (int i0 = blockIdx.y * RB; i0 < N; i0 += gridDim.y * RB) {
+      const int64_t o0 = (int64_t)i0 * N + j;
+      const int64_t h0 = (int64_t)i0 * (N - 1) + j;
+      float xc[RB + 1], xr[RB], ph[RB], pv[RB];
+#pragma unroll
+      for (int t = 0; t <= RB; ++t) xc[t] = (i0 + t < N) ? xbar[o0 + (int64_t)t * N] : 0.f;
+#pragma unroll
+      for (int t = 0; t < RB; ++t) {
+        const bool in = i0 + t < N;
+        xr[t] = (hr && in) ? xbar[o0 + (int64_t)t * N + 1] : 0.f;
+        ph[t] = (hr && in) ? qh[h0 + (int64_t)t * (N - 1)] : 0.f;
+        pv[t] = (i0 + t < N - 1) ? qv[o0 + (int64_t)t * N] : 0.f;
+      }
+#pragma unroll
+      for (int t = 0; t < RB; ++t) {
+        const int i = i0 + t;
+        if (i < N) {
+          if (hr) qh[h0 + (int64_t)t * (N - 1)] = pdhg_q_entry(sig, lam, xc[t] - xr[t], ph[t], s1, s3);
+          if (i < N - 1) qv[o0 + (int64_t)t * N] = pdhg_q_entry(sig, lam, xc[t] - xc[t + 1], pv[t], s1, s3);
+        }
+      }
+    }
+  }
+  s1 = block_sum<NT>(s1, red);
+  s3 = block_sum<NT>(s3, red);
+  if (threadIdx.x == 0) {
+    const size_t blk = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
+    partials[blk * 8 + 1] = s1;
+    partials[blk * 8 + 3] = s3;
+  }
+}
+
+// x_new may be x (a pixel is read and then written by the same thread): no __restrict__ on the two
+template <bool HAS_XT>
+__global__ __launch_bounds__(NT) void k_pdhg_tv_primal(const float* x, const float* __restrict__ z, const float* __restrict__ q,
+                                                       float* x_new, float* __restrict__ xbar, const float* __restrict__ x_true, int N,
+                                                       float tau, float lo, float hi, double* __restrict__ partials) {
+  __shared__ double red[NT / 64];
+  const float* __restrict__ qh = q;
+  const float* __restrict__ qv = q + (int64_t)N * (N - 1);
+  const int j = blockIdx.x * NT + threadIdx.x;
+  double s4 = 0.0, s5 = 0.0, s6 = 0.0, s7 = 0.0;
+  if (j < N) {
+    const bool hr = j < N - 1, hl = j > 0;
+    for (int i0 = blockIdx.y * RB; i0 < N; i0 += gridDim.y * RB) {
+      const int64_t o0 = (int64_t)i0 * N + j;
+      const int64_t h0 = (int64_t)i0 * (N - 1) + j;
+      float hc[RB], hp[RB], v[RB + 1], xv[RB], zv[RB], tv[RB];
+#pragma unroll
+      for (int t = 0; t <= RB; ++t) {      // v[t] = qv[i0 + t - 1][j]
+        const int i = i0 + t - 1;
+        v[t] = (i >= 0 && i < N - 1) ? qv[o0 + (int64_t)(t - 1) * N] : 0.f;
+      }
+#pragma unroll
+      for (int t = 0; t < RB; ++t) {
+        const bool in = i0 + t < N;
+        hc[t] = (in && hr) ? qh[h0 + (int64_t)t * (N - 1)] : 0.f;
+        hp[t] = (in && hl) ? qh[h0 + (int64_t)t * (N - 1) - 1] : 0.f;
+        xv[t] = in ? x[o0 + (int64_t)t * N] : 0.f;
+        zv[t] = in ? z[o0 + (int64_t)t * N] : 0.f;
+        tv[t] = (HAS_XT && in) ? x_true[o0 + (int64_t)t * N] : 0.f;
+      }
+#pragma unroll
+      for (int t = 0; t < RB; ++t) {
+        const int i = i0 + t;
+        if (i < N) {
+          float acc = 0.f;                 // k_d2_adj's order
+          if (hr) acc += hc[t];
+          if (hl) acc -= hp[t];
+          if (i < N - 1) acc += v[t + 1];
+          if (i > 0) acc -= v[t];
+          float xn, xb;
+          pdhg_x_entry<HAS_XT>(tau, lo, hi, xv[t], zv[t] + acc, tv[t], xn, xb, s4, s5, s6, s7);
+          x_new[o0 + (int64_t)t * N] = xn;
+          xbar[o0 + (int64_t)t * N] = xb;
+        }
+      }
+    }
+  }
+  s4 = block_sum<NT>(s4, red);
+  s5 = block_sum<NT>(s5, red);
+  if (HAS_XT) s6 = block_sum<NT>(s6, red);
+  s7 = block_sum<NT>(s7, red);
+  if (threadIdx.x == 0) {
+    const size_t blk = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
+    partials[blk * 8 + 4] = s4;
+    partials[blk * 8 + 5] = s5;
+    partials[blk * 8 + 6] = HAS_XT ? s6 : 0.0;
+    partials[blk * 8 + 7] = s7;
+  }
+}
+
 // ------------------------------------------------------------------------------------------------ 2-D operator
 struct D2Impl {
   int N;
@@ -539,4 +647,49 @@ int trk_spacetime_set_halo(trk_op* op, const float* x_next, const float* y_prev)
   return TRK_OK;
 }
 
+// ---- PDHG's fused forms (the 2-D operator only; pdhg.hip chains them)
+int trk_pdhg_fused_caps(const trk_op* L, int* can) {
+  TRK_REQUIRE(L && can, "trk_pdhg_fused_caps: NULL argument");
+  *can = L->kind == 3 ? 1 : 0;
+  return TRK_OK;
+}
+
+int trk_pdhg_tv_dual(trk_op* L, double sigma, double lam, const float* xbar, float* q, double* partials, int capacity_blocks,
+                     int* n_blocks, trk_stream st) {
+  TRK_REQUIRE(L && xbar && q && partials && n_blocks, "trk_pdhg_tv_dual: NULL argument");
+  if (L->kind != 3) return fail(TRK_EUNSUPPORTED, "trk_pdhg_tv_dual: the fused forms take a handle from trk_deriv2d_create only");
+  TRK_REQUIRE(sigma > 0.0 && sigma < __builtin_inf(), "trk_pdhg_tv_dual: sigma must be finite and > 0");
+  TRK_REQUIRE(lam >= 0.0 && lam < __builtin_inf(), "trk_pdhg_tv_dual: lam must be finite and >= 0");
+  TRK_REQUIRE(q != xbar, "trk_pdhg_tv_dual: q must not alias xbar");
+  const int N = static_cast<D2Impl*>(L->impl)->N;
+  const Grid2 g2 = grid2(N, 1, true);
+  TRK_REQUIRE(g2.per_frame <= capacity_blocks, "trk_pdhg_tv_dual: partial buffer too small (%d blocks needed)", g2.per_frame);
+  *n_blocks = g2.per_frame;
+  hipLaunchKernelGGL(k_pdhg_tv_dual, g2.g, dim3(NT), 0, (hipStream_t)st, xbar, q, N, (float)sigma, (float)lam, partials);
+  TRK_LAUNCH_CHECK();
+  return TRK_OK;
+}
+
+int trk_pdhg_tv_primal(trk_op* L, double tau, double lo, double hi, const float* x, const float* z, const float* q, float* x_new,
+                       float* xbar, const float* x_true, double* partials, int capacity_blocks, int* n_blocks, trk_stream st) {
+  TRK_REQUIRE(L && x && z && q && x_new && xbar && partials && n_blocks, "trk_pdhg_tv_primal: NULL argument");
+  if (L->kind != 3) return fail(TRK_EUNSUPPORTED, "trk_pdhg_tv_primal: the fused forms take a handle from trk_deriv2d_create only");
+  TRK_REQUIRE(tau > 0.0 && tau < __builtin_inf(), "trk_pdhg_tv_primal: tau must be finite and > 0");
+  TRK_REQUIRE(lo <= hi, "trk_pdhg_tv_primal: need lo <= hi (either may be infinite)");
+  TRK_REQUIRE(xbar != x && xbar != x_new && xbar != z && xbar != q && xbar != x_true,
+              "trk_pdhg_tv_primal: xbar must not alias another operand");
+  TRK_REQUIRE(x_new != z && x_new != q && x_new != x_true, "trk_pdhg_tv_primal: x_new may alias x only");
+  const int N = static_cast<D2Impl*>(L->impl)->N;
+  const Grid2 g2 = grid2(N, 1, true);
+  TRK_REQUIRE(g2.per_frame <= capacity_blocks, "trk_pdhg_tv_primal: partial buffer too small (%d blocks needed)", g2.per_frame);
+  *n_blocks = g2.per_frame;
+  hipStream_t s = (hipStream_t)st;
+  if (x_true) hipLaunchKernelGGL((k_pdhg_tv_primal<true>), g2.g, dim3(NT), 0, s, x, z, q, x_new, xbar, x_true, N, (float)tau, (float)lo, (float)hi, partials);
+  else hipLaunchKernelGGL((k_pdhg_tv_primal<false>), g2.g, dim3(NT), 0, s, x, z, q, x_new, xbar, x_true, N, (float)tau, (float)lo, (float)hi, partials);
+  TRK_LAUNCH_CHECK();
+  return TRK_OK;
+}
+
 }  // extern "C"
+
+int trk::pdhg_tv_blocks(const trk_op* L) { return (L && L->kind == 3) ? grid2(static_cast<D2Impl*>(L->impl)->N, 1, true).per_frame : 0; }

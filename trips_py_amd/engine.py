@@ -710,6 +710,71 @@ class HipEngine:
         _lib.check(rc, "trk_mrnsd_iterate")
         return c.value
 
+    # ------------------------------------------------------------------ PDHG (pdhg.hip, tvops.hip; the rows of 8 partials: include/trk.h)
+    def pdhg_blocks(self, m, n, rows, fused_handle=None):
+        """The largest block count of an iteration's kernels: the capacity (in rows of 8 doubles) its partials need."""
+        c = ctypes.c_int(0)
+        _lib.check(self.lib.trk_pdhg_blocks(int(m), int(n), int(rows), fused_handle, ctypes.byref(c)), "trk_pdhg_blocks")
+        return c.value
+
+    def pdhg_fused_caps(self, handle):
+        can = ctypes.c_int(0)
+        _lib.check(self.lib.trk_pdhg_fused_caps(handle, ctypes.byref(can)), "trk_pdhg_fused_caps")
+        return can.value
+
+    def pdhg_dual_p(self, sigma, w, b, p, partials, capacity):
+        """p = (p + sigma (w - b)) / (1 + sigma) in place; slots 0, 2.  Returns the block count (as the four below)."""
+        c = ctypes.c_int(0)
+        rc = self.lib.trk_pdhg_dual_p(p.numel(), float(sigma), w.data_ptr(), b.data_ptr(), p.data_ptr(), _ptr(partials), int(capacity),
+                                      ctypes.byref(c), self.stream())
+        _lib.check(rc, "trk_pdhg_dual_p")
+        return c.value
+
+    def pdhg_dual_q(self, sigma, lam, u, q, partials, capacity):
+        """q = clip(q + sigma u, -lam, lam) in place; slots 1, 3."""
+        c = ctypes.c_int(0)
+        rc = self.lib.trk_pdhg_dual_q(q.numel(), float(sigma), float(lam), u.data_ptr(), q.data_ptr(), _ptr(partials), int(capacity),
+                                      ctypes.byref(c), self.stream())
+        _lib.check(rc, "trk_pdhg_dual_q")
+        return c.value
+
+    def pdhg_primal(self, tau, lo, hi, x, z, v, x_new, xbar, x_true, partials, capacity):
+        """x_new = clip(x - tau (z + v), lo, hi), xbar = 2 x_new - x; v may be None; slots 4..7."""
+        c = ctypes.c_int(0)
+        rc = self.lib.trk_pdhg_primal(x.numel(), float(tau), float(lo), float(hi), x.data_ptr(), z.data_ptr(),
+                                      None if v is None else v.data_ptr(), x_new.data_ptr(), xbar.data_ptr(),
+                                      None if x_true is None else x_true.data_ptr(), _ptr(partials), int(capacity), ctypes.byref(c),
+                                      self.stream())
+        _lib.check(rc, "trk_pdhg_primal")
+        return c.value
+
+    def pdhg_tv_dual(self, handle, sigma, lam, xbar, q, partials, capacity):
+        """pdhg_dual_q with u = L xbar formed in registers (a FirstDerivative2D handle)."""
+        c = ctypes.c_int(0)
+        rc = self.lib.trk_pdhg_tv_dual(handle, float(sigma), float(lam), xbar.data_ptr(), q.data_ptr(), _ptr(partials), int(capacity),
+                                       ctypes.byref(c), self.stream())
+        _lib.check(rc, "trk_pdhg_tv_dual")
+        return c.value
+
+    def pdhg_tv_primal(self, handle, tau, lo, hi, x, z, q, x_new, xbar, x_true, partials, capacity):
+        """pdhg_primal with v = L^T q gathered in the kernel (a FirstDerivative2D handle)."""
+        c = ctypes.c_int(0)
+        rc = self.lib.trk_pdhg_tv_primal(handle, float(tau), float(lo), float(hi), x.data_ptr(), z.data_ptr(), q.data_ptr(),
+                                         x_new.data_ptr(), xbar.data_ptr(), None if x_true is None else x_true.data_ptr(),
+                                         _ptr(partials), int(capacity), ctypes.byref(c), self.stream())
+        _lib.check(rc, "trk_pdhg_tv_primal")
+        return c.value
+
+    def pdhg_iterate(self, hA, hL, k_first, n_iters, sigma, tau, lam, lo, hi, fused, b, p, q, w, u, z, v, X, keep, x_prev, xbar,
+                     x_true, NP, np_cap):
+        """n_iters PDHG iterations in one library call."""
+        rc = self.lib.trk_pdhg_iterate(hA, hL, int(k_first), int(n_iters), float(sigma), float(tau), float(lam), float(lo), float(hi),
+                                       int(bool(fused)), b.data_ptr(), p.data_ptr(), q.data_ptr(), w.data_ptr(),
+                                       None if u is None else u.data_ptr(), z.data_ptr(), None if v is None else v.data_ptr(),
+                                       X.data_ptr(), X.stride(0), int(bool(keep)), x_prev.data_ptr(), xbar.data_ptr(),
+                                       None if x_true is None else x_true.data_ptr(), _ptr(NP), int(np_cap), self.stream())
+        _lib.check(rc, "trk_pdhg_iterate")
+
     def finalize_batched(self, partials, nblocks, nvals, batches, out, out_stride):
         rc = self.lib.trk_finalize_batched(_ptr(partials), int(nblocks), int(nvals), int(batches), _ptr(out), int(out_stride),
                                            self.stream())

@@ -804,6 +804,38 @@ class Identity(LinearOperator):
             self.engine.nrm2sq(y2.reshape(-1), sumsq)
 
 
+def operator_norm_sq(ops, iters=30, seed=0):
+    """An estimate of ||K||^2 for K = the operators of `ops` stacked by rows: the largest eigenvalue of sum_O O^T O, by `iters` steps
+    of power iteration from `default_rng(seed).standard_normal(n)` rounded to fp32.  Step j normalises v, forms y = sum_O O^T (O v)
+    with the engine's apply / axpby / norm kernels and takes the Rayleigh quotient sum_O ||O v||^2 / ||v||^2; the next v is y.
+    Returns the last quotient — it approaches ||K||^2 FROM BELOW (PDHG's default steps leave room for that: solvers/PDHG.py).
+    One read-back, after the last step."""
+    from .engine import Coef
+    ops = [ops] if isinstance(ops, LinearOperator) else list(ops)
+    if not ops or any(o.shape[1] != ops[0].shape[1] for o in ops):
+        raise ValueError("operator_norm_sq: the operators must share their column count")
+    iters = int(iters)
+    if iters < 1:
+        raise ValueError("operator_norm_sq needs iters >= 1")
+    eng, n = ops[0].engine, ops[0].shape[1]
+    y = eng.to_vec(np.random.default_rng(seed).standard_normal(n).astype(np.float32))
+    v, t = eng.empty(n), eng.empty(n)
+    outs = [eng.empty(o.shape[0]) for o in ops]
+    T = eng.scalars(2 + len(ops))                       # ||y||^2, ||v||^2, ||O v||^2 per operator
+    for _ in range(iters):
+        eng.nrm2sq(y, T.ref(0))
+        eng.scale(Coef(1.0, den=T.ref(0), sqrt_den=True), y, v, sumsq=T.ref(1))
+        for i, (o, w) in enumerate(zip(ops, outs)):
+            o.apply(v, out=w, sumsq=T.ref(2 + i))
+            if i == 0:
+                o.apply(w, out=y, transpose=True)
+            else:
+                o.apply(w, out=t, transpose=True)
+                eng.axpby(1.0, y, 1.0, t, y)
+    Th = T.host()
+    return float(Th[2:].sum() / Th[1])
+
+
 def is_identity(A):
     """Host predicate selecting the L = I branch (trips/utilities/utils.py:47-62)."""
     if isinstance(A, Identity):

@@ -8,7 +8,7 @@ With r = b - A x, g = -A^T r and s = -(x . g) (steepest descent in the metric sc
         r -= alpha u ; the next gamma = -<g, s> and bound = min_{s_i < 0} x_i / -s_i, and the reported norms
 Vectors are fp32, scalars and reductions fp64; nothing visits the host unless a stopping rule asks (include/trk.h: the layout of S).
 Not built: sharded MRNSD, a periodic refresh of g from a true product, the s / r updates fused into the blur's two-operand form,
-weighted or Poisson variants, box constraints.
+weighted or Poisson variants, box constraints (solvers.PDHG takes a box).
 """
 import numpy as np
 import torch

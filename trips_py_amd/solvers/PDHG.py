@@ -1,0 +1,233 @@
+"""PDHG on the HIP engine: min_x 1/2 ||A x - b||^2 + lam ||L x||_1 subject to lower <= x <= upper — the exact l1 / anisotropic TV term
+and a box in one solve, by the primal-dual hybrid gradient iteration (Chambolle and Pock 2011, algorithm 1, theta = 1; CIL's PDHG).
+
+With K = [A; L], duals p and q (zero at the start), x_0 the caller's start projected onto the box and xbar_0 = x_0, per iteration:
+    w = A xbar ; p = (p + sigma (w - b)) / (1 + sigma)                      (trk_pdhg_dual_p)
+    u = L xbar ; q = clip(q + sigma u, -lam, lam)                           (trk_pdhg_dual_q, or trk_pdhg_tv_dual: u in registers)
+    z = A^T p ; v = L^T q ; x = clip(x - tau (z + v), lower, upper) ; xbar = 2 x - x_previous
+                                                                            (trk_pdhg_primal, or trk_pdhg_tv_primal: v gathered)
+sigma, tau and lam are host constants, so nothing is read back inside the loop: a whole solve is one enqueue (trk_pdhg_iterate).
+Vectors are fp32, the reported sums fp64 (include/trk.h: the operations and the layout of S).  It converges for
+sigma tau ||K||^2 < 1.
+Not built: isotropic TV, fused forms for SpaceTimeDerivative / Framelet2D (they run on the generic path), sharded PDHG, diagonal
+preconditioning or adaptive step balancing (`ratio` is the only knob), other data terms.
+"""
+import numpy as np
+
+from .._io import Formatter, History, as_operator
+from ..operators import operator_norm_sq
+from .CGLS import _row_of
+from .MRNSD import MRNSDRun, _host
+
+
+class PDHGRun:
+    """The PDHG iteration as an object, like MRNSDRun: `step()` enqueues one iteration from Python, `run(n)` n of them in one library
+    call when A and L both have handles (trk_pdhg_iterate: the same kernels, the same bits), `rows()` / `row(k)` download the sums.
+
+    Row k (1-based) at S + 8k = [||A xbar - b||^2, sum |L xbar|, ||p_k - p_{k-1}||^2, ||q_k - q_{k-1}||^2, ||x_k||^2,
+    ||x_k - x_{k-1}||^2, ||x_k - x_true||^2, entries of x_k on a bound], the first two at xbar_{k-1} = 2 x_{k-1} - x_{k-2}: the point
+    iteration k applies A and L to.  `fused`: None = the fused first-difference kernels where L takes them, True / False forces."""
+
+    def __init__(self, A, b, L, lam, sigma, tau, lower, upper, x0, max_iter, x_true=None, history=True, fused=None):
+        self.A = A = as_operator(A)
+        self.L = L = as_operator(L, "L")
+        self.eng = eng = A.engine
+        if eng.world > 1:
+            raise NotImplementedError("PDHG is not built for unknowns spread over ranks (eng.world > 1)")
+        m, n = A.shape
+        rows = L.shape[0]
+        if L.shape[1] != n:
+            raise ValueError(f"L has {L.shape[1]} columns, A has {n}")
+        self.lam, self.sigma, self.tau = float(lam), float(sigma), float(tau)
+        self.lo, self.hi = float(lower), float(upper)
+        if not (np.isfinite(self.lam) and self.lam >= 0):
+            raise ValueError("PDHG: lam must be finite and >= 0")
+        if not (np.isfinite(self.sigma) and np.isfinite(self.tau) and self.sigma > 0 and self.tau > 0):
+            raise ValueError("PDHG: sigma and tau must be finite and > 0")
+        if not self.lo <= self.hi:
+            raise ValueError("PDHG: need lower <= upper")
+        self.max_iter = max_iter = int(max_iter)
+        self.bv = eng.to_vec(b, m)
+        self.xt = None if x_true is None else eng.to_vec(x_true, n)
+        can = bool(hasattr(L, "_h") and hasattr(eng, "pdhg_fused_caps") and eng.pdhg_fused_caps(L._h))
+        if fused and not can:
+            raise ValueError("PDHG: fused=True needs a FirstDerivative2D regulariser on the HIP engine")
+        self.fused = can if fused is None else bool(fused)
+        # the start, projected onto the box in fp32 (the bounds as the kernels round them)
+        x0h = np.zeros(n, dtype=np.float32) if x0 is None else _host(x0).astype(np.float32).reshape(-1)
+        if x0h.size != n:
+            raise ValueError(f"x0 has {x0h.size} entries, expected {n}")
+        self.x_cur = eng.to_vec(np.clip(x0h, np.float32(self.lo), np.float32(self.hi)))
+        self.xbar = self.x_cur.clone()
+        self.hist = History(eng, history, max_iter, n, "PDHG xHistory")
+        self.X = self.hist.X
+        self.p, self.w = eng.zeros(m), eng.empty(m)
+        self.q, self.z = eng.zeros(rows), eng.empty(n)
+        self.u, self.v = (None, None) if self.fused else (eng.empty(rows), eng.empty(n))
+        self.cap = eng.pdhg_blocks(m, n, rows, L._h if self.fused else None)
+        self.NP = eng.scalars(8 * self.cap * max(1, max_iter))     # zeroed: a kernel writes only its slots of its blocks' rows
+        self.S = eng.scalars(8 * (max_iter + 1))
+        self.B = eng.scalars(1)                                    # ||b||^2
+        eng.nrm2sq(self.bv, self.B.ref(0))
+        self.k = 0
+        self._final = 0
+
+    def slot(self, k):
+        """The device row holding iterate k (0-based)."""
+        return self.X[self.hist.slot(k)]
+
+    def step(self):
+        eng, A, L = self.eng, self.A, self.L
+        self.k += 1
+        k = self.k
+        part = self.NP.ref(8 * self.cap * (k - 1))
+        x_new = self.hist.row(k - 1)
+        A.apply(self.xbar, out=self.w)
+        eng.pdhg_dual_p(self.sigma, self.w, self.bv, self.p, part, self.cap)
+        if self.fused:
+            eng.pdhg_tv_dual(L._h, self.sigma, self.lam, self.xbar, self.q, part, self.cap)
+        else:
+            L.apply(self.xbar, out=self.u)
+            eng.pdhg_dual_q(self.sigma, self.lam, self.u, self.q, part, self.cap)
+        A.apply(self.p, out=self.z, transpose=True)
+        if self.fused:
+            eng.pdhg_tv_primal(L._h, self.tau, self.lo, self.hi, self.x_cur, self.z, self.q, x_new, self.xbar, self.xt, part, self.cap)
+        else:
+            L.apply(self.q, out=self.v, transpose=True)
+            eng.pdhg_primal(self.tau, self.lo, self.hi, self.x_cur, self.z, self.v, x_new, self.xbar, self.xt, part, self.cap)
+        self.x_cur = x_new
+        self.hist.pushed(k - 1)
+
+    _run_c_loop = MRNSDRun._run_c_loop                 # the chunking of a streamed history: CGLSRun's
+
+    def run(self, n_steps):
+        """Enqueue `n_steps` iterations: one library call where A and L both have handles, else `step()` by `step()`."""
+        n_steps = min(int(n_steps), self.max_iter - self.k)
+        if n_steps <= 0:
+            return
+        eng = self.eng
+        if hasattr(self.A, "_h") and hasattr(self.L, "_h") and hasattr(eng, "pdhg_iterate"):
+            def call(k_first, n, X, keep):
+                eng.pdhg_iterate(self.A._h, self.L._h, k_first, n, self.sigma, self.tau, self.lam, self.lo, self.hi, self.fused, self.bv,
+                                 self.p, self.q, self.w, self.u, self.z, self.v, X, keep, self.x_cur, self.xbar, self.xt,
+                                 self.NP.ref(0), self.cap)
+                self.x_cur = _row_of(X, k_first + n - 2, keep)
+            self._run_c_loop(n_steps, call)
+        else:
+            for _ in range(n_steps):
+                self.step()
+
+    def _finish(self):
+        """The block partials of the iterations not summed yet into their rows of S."""
+        if self._final == self.k:
+            return
+        f = self._final
+        self.eng.finalize_batched(self.NP.ref(8 * self.cap * f), self.cap, 8, self.k - f, self.S.ref(8 * (f + 1)), 8)
+        self._final = self.k
+
+    def row(self, k):
+        """Row k of S (host sync)."""
+        self._finish()
+        return self.S.host(8 * k, 8 * k + 8)
+
+    def rows(self):
+        """The k rows on the host."""
+        self._finish()
+        return self.S.host()[8:8 * (self.k + 1)].reshape(self.k, 8)
+
+    def b_norm(self):
+        return float(np.sqrt(self.B.host(0, 1)[0]))
+
+    def objective_at(self, x):
+        """1/2 ||A x - b||^2 + lam ||L x||_1 at a device vector x, from one pair of products (the sums of the dual kernels on scratch
+        duals; the state of the run is left alone)."""
+        eng = self.eng
+        w, u = self.A.apply(x), self.L.apply(x)
+        part, out = eng.scalars(8 * self.cap), eng.scalars(8)
+        eng.pdhg_dual_p(self.sigma, w, self.bv, eng.zeros(w.numel()), part.ref(0), self.cap)
+        eng.pdhg_dual_q(self.sigma, self.lam, u, eng.zeros(u.numel()), part.ref(0), self.cap)
+        eng.finalize_batched(part.ref(0), self.cap, 8, 1, out.ref(0), 8)
+        s = out.host()
+        return 0.5 * float(s[0]) + self.lam * float(s[1])
+
+
+def pdhg_steps(normK2, ratio=1.0):
+    """(sigma, tau) with sigma tau normK2 = 0.95^2 and sigma / tau = ratio."""
+    tau = 0.95 / np.sqrt(float(normK2) * float(ratio))
+    return float(ratio) * tau, tau
+
+
+def PDHG(A, b, L, lam, max_iter, tol=0, x0=None, x_true=None, lower=0.0, upper=np.inf, sigma=None, tau=None, normK2=None, ratio=1.0,
+         **kwargs):
+    """Primal-dual hybrid gradient: min 1/2 ||A x - b||^2 + lam ||L x||_1 subject to lower <= x <= upper.
+
+    A, L: LinearOperators with the same column count (L = Identity: plain l1; FirstDerivative2D: anisotropic TV, on fused kernels);
+    b: (m,) / (m,1); x0: (n,) / (n,1) or None (zeros), projected onto the box; lower / upper: scalars, -inf / +inf allowed.
+    Steps: sigma and tau as given; if not both are, sigma tau normK2 = 0.95^2 and sigma / tau = ratio, with normK2 the caller's number
+    or else operator_norm_sq([A, L], iters=30, seed=0) — an estimate from below, for which the 0.95 leaves room down to 0.9025 of the
+    true ||K||^2.  Returns (x, info) with info keys
+        xHistory, its,
+        relResidual   ||x_k - x_{k-1}|| / ||x_k||,
+        Rnrm          ||A xbar_{k-1} - b|| / ||b||   and
+        objective     1/2 ||A xbar_{k-1} - b||^2 + lam ||L xbar_{k-1}||_1 — both AT THE EXTRAPOLATED POINT xbar_{k-1} = 2 x_{k-1} - x_{k-2}
+                      iteration k applies A and L to (they cost no product of their own), not at x_k,
+        dualChange    sqrt(||p_k - p_{k-1}||^2 + ||q_k - q_{k-1}||^2),
+        active        the number of entries of x_k on a bound,
+        relError      ||x_k - x_true|| / ||x_true|| when x_true is given (as MRNSD),
+        sigma, tau, normK2 (None when both steps were given without it),
+        objectiveFinal  the objective at the returned x, from one extra pair of products after the loop.
+    Stopping: tol = 0 runs max_iter iterations in one enqueue; tol > 0 reads a row back every iteration and stops at
+    relResidual <= tol; with delta= (and eta=1.01) it stops when ||A xbar - b|| <= eta delta.
+    Engine-only kwargs: history — as for CGLS (trips_py_amd._io.History); fused — None / True / False (PDHGRun); delta, eta.
+    """
+    max_iter = int(max_iter)
+    if max_iter <= 0:
+        raise ValueError("PDHG needs max_iter >= 1")
+    fmt = Formatter(b)
+    A, L = as_operator(A), as_operator(L, "L")
+    if A.engine.world > 1:
+        raise NotImplementedError("PDHG is not built for unknowns spread over ranks (eng.world > 1)")
+    if L.shape[1] != A.shape[1]:
+        raise ValueError(f"L has {L.shape[1]} columns, A has {A.shape[1]}")
+    lam = float(lam)
+    if not (np.isfinite(lam) and lam >= 0):
+        raise ValueError("PDHG: lam must be finite and >= 0")
+    if not float(lower) <= float(upper):
+        raise ValueError("PDHG: need lower <= upper")
+    for name, val in (("sigma", sigma), ("tau", tau), ("normK2", normK2), ("ratio", ratio)):
+        if val is not None and not (np.isfinite(val) and val > 0):
+            raise ValueError(f"PDHG: {name} must be finite and > 0")
+    if sigma is None or tau is None:
+        if normK2 is None:
+            normK2 = operator_norm_sq([A, L], iters=30, seed=0)
+            if not (np.isfinite(normK2) and normK2 > 0):
+                raise ValueError("PDHG: the estimate of ||K||^2 is not positive: A and L are both zero?")
+        sigma, tau = pdhg_steps(normK2, ratio)
+    delta = kwargs.get("delta", None)
+    eta = float(kwargs.get("eta", 1.01))
+    run = PDHGRun(A, b, L, lam, sigma, tau, lower, upper, x0, max_iter, x_true, kwargs.get("history", True), kwargs.get("fused", None))
+    if tol == 0 and delta is None:
+        run.run(max_iter)                       # nothing is read back inside the loop -> one enqueue
+    else:
+        while run.k < max_iter:
+            run.step()
+            h = run.row(run.k)
+            if tol != 0 and np.sqrt(h[5]) <= tol * np.sqrt(h[4]):
+                break
+            if delta is not None and np.sqrt(h[0]) <= eta * float(delta):
+                break
+    rows = run.rows()
+    k, x_fin = run.k, run.x_cur
+    with np.errstate(divide="ignore", invalid="ignore"):
+        info = {"xHistory": run.hist.collect(fmt, k), "its": k,
+                "relResidual": list(np.sqrt(rows[:, 5]) / np.sqrt(rows[:, 4])),
+                "Rnrm": list(np.sqrt(rows[:, 0]) / run.b_norm()),
+                "objective": list(0.5 * rows[:, 0] + lam * rows[:, 1]),
+                "dualChange": list(np.sqrt(rows[:, 2] + rows[:, 3])),
+                "active": [int(c) for c in rows[:, 7]],
+                "sigma": float(sigma), "tau": float(tau), "normK2": None if normK2 is None else float(normK2),
+                "objectiveFinal": run.objective_at(x_fin)}
+    if run.xt is not None:
+        nxt = float(np.linalg.norm(_host(run.xt).astype(np.float64)))
+        info["relError"] = list(np.sqrt(rows[:, 6]) / nxt)
+    return fmt.vec(x_fin), info
