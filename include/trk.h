@@ -697,7 +697,31 @@ int trk_mrnsd_iterate(trk_op* A, int k_first, int n_iters, float* g, float* s, f
  * trk_pdhg_blocks: the largest block count of an iteration's kernels (L_fused: the handle of the fused forms, or NULL).
  * trk_pdhg_iterate: iterations k_first .. k_first + n_iters - 1 enqueued by one call, nothing read back.  Iteration k takes x_{k-1}
  *   from x_prev (k = k_first) or the slot it wrote, writes iterate k to slot k-1 of X (keep_history) or (k-1) & 1, and its partials
- *   to NP + 8 np_capacity_blocks (k-1) (zeroed by the caller).  With `fused` u and v are unused (may be NULL): five launches. */
+ *   to NP + 8 np_capacity_blocks (k-1) (zeroed by the caller).  With `fused` u and v are unused (may be NULL): five launches.
+ *
+ * ISOTROPIC TV: lam sum_g ||(L x)_g||_2 in place of lam ||L x||_1, the groups g a partition of the rows of L given by a geometry
+ * (N, frames) on the row layout of the first-difference operators: `frames` blocks of 2 N (N - 1) rows, each H (N x (N-1),
+ * x[i][j] - x[i][j+1]) then V ((N-1) x N, x[i][j] - x[i+1][j]), followed by a tail of rows - frames 2 N (N - 1) >= 0 further rows.
+ *   pair:    {H[i][j], V[i][j]} of a frame for i < N - 1 and j < N - 1
+ *   single:  H[N-1][j] (last image row), V[i][N-1] (last image column) and every tail row; its norm is its absolute value and its
+ *            update is the dual q entry above, bit for bit
+ * (trk_deriv2d_create: frames = 1, no tail; trk_spacetime_create: frames = nt, the temporal rows the tail: spatially isotropic,
+ * temporally l1.)  Only the dual update of q changes: q' = the projection of each group of q + sigma u onto the 2-norm ball of
+ * radius lam.  The fp32 operations of a pair, in this order (sqrtf and / correctly rounded, no reciprocal shortcuts):
+ *   th = fmaf(sf, uh, qh) ;  tv = fmaf(sf, uv, qv)
+ *   m2 = fmaf(th, th, tv * tv) ;  m = sqrtf(m2)
+ *   if (m <= lf) { qh' = th ; qv' = tv }  else { s = lf / m ;  qh' = th * s ;  qv' = tv * s }
+ * (lam = 0: m = 0 keeps t = 0, m > 0 gives s = 0.)  Slot 1 becomes sum_g ||u_g||_2, a pair's term sqrt((double)uh * uh +
+ * (double)uv * uv); slot 3 stays ||q' - q||^2.  p, the primal update, xbar, the other slots and the steps are as above.
+ * trk_pdhg_dual_q_iso: u = L xbar in memory, any L with that row layout.  The grouped rows by one kernel (one thread per image
+ *   column, blockIdx.z = frame), the tail by trk_pdhg_dual_q's kernel on the slices u + off, q + off (no alignment assumed); the
+ *   tail's blocks take the rows of partials behind the grouped kernel's.  *n_blocks: the rows that wrote, both launches.
+ * trk_pdhg_tv_dual_iso: the fused form for a handle from trk_deriv2d_create (any other: TRK_EUNSUPPORTED) — trk_pdhg_tv_dual's
+ *   loads, stores and grid, the two entries of a pixel joined in registers; the same bits in q as trk_pdhg_dual_q_iso on that
+ *   handle's product.  trk_pdhg_tv_primal follows it unchanged (the primal is linear in q).
+ * trk_pdhg_blocks_iso: trk_pdhg_blocks for the isotropic forms (L_fused NULL: grouped blocks + tail blocks count for the dual).
+ * trk_pdhg_iterate_iso: trk_pdhg_iterate with the geometry.  Five launches with `fused` (then (N, frames) must be the handle's
+ *   (N, 1)), seven without a tail and eight with one.  L must be rows x frames N^2 with rows >= frames 2 N (N - 1). */
 int trk_pdhg_blocks(int64_t m, int64_t n, int64_t rows, const trk_op* L_fused, int* blocks);
 int trk_pdhg_dual_p(int64_t m, double sigma, const float* w, const float* b, float* p, double* partials, int capacity_blocks,
                     int* n_blocks, trk_stream stream);
@@ -714,6 +738,15 @@ int trk_pdhg_iterate(trk_op* A, trk_op* L, int k_first, int n_iters, double sigm
                      int fused, const float* b, float* p, float* q, float* w, float* u, float* z, float* v, float* X, int64_t x_ld,
                      int keep_history, const float* x_prev, float* xbar, const float* x_true, double* NP, int np_capacity_blocks,
                      trk_stream stream);
+int trk_pdhg_blocks_iso(int64_t m, int64_t n, int64_t rows, int N, int frames, const trk_op* L_fused, int* blocks);
+int trk_pdhg_dual_q_iso(int N, int frames, int64_t rows, double sigma, double lam, const float* u, float* q, double* partials,
+                        int capacity_blocks, int* n_blocks, trk_stream stream);
+int trk_pdhg_tv_dual_iso(trk_op* L, double sigma, double lam, const float* xbar, float* q, double* partials, int capacity_blocks,
+                         int* n_blocks, trk_stream stream);
+int trk_pdhg_iterate_iso(trk_op* A, trk_op* L, int N, int frames, int k_first, int n_iters, double sigma, double tau, double lam,
+                         double lo, double hi, int fused, const float* b, float* p, float* q, float* w, float* u, float* z, float* v,
+                         float* X, int64_t x_ld, int keep_history, const float* x_prev, float* xbar, const float* x_true, double* NP,
+                         int np_capacity_blocks, trk_stream stream);
 
 /* ---------------------------------------------------------------- tall-skinny basis ops */
 /* h[j] = sum_i w2[i] * V[j][i] * r[i], j < k  (w2 may be NULL = 1).  One pass over V.

@@ -1,6 +1,6 @@
 """PDHG iteration rates on the device: a record, not a gate.
 
-    python tools/pdhg_rate.py [--out profiles/pdhg/pdhg_rates.json] [--steps K] [--warmup W]
+    python tools/pdhg_rate.py [--tv iso] [--out profiles/pdhg/pdhg_rates.json] [--steps K] [--warmup W]
 
 Seeded data; per case W warm-up iterations, then K iterations between two device events, the window closed by a synchronise;
 the median of three windows.  Cases: the 9x9 reflect Gaussian blur at 4096^2 and 512^2 with the 2-D first differences (anisotropic
@@ -8,7 +8,9 @@ TV), box [0, inf).  Reported per case: iterations/s of PDHGRun.run (one library 
 and on the generic path (7 launches, 100n), the model bytes over the measured time, each new kernel alone with its own byte count,
 and, for scale from the same run, MRNSDRun.run and MMGKS (projection_dim 3, 30 iterations, lambda fixed) iterations/s.
 Model bytes, square problem, rows of L = 2n: A and A^T 8n each, L and L^T 12n each, dual p 16n, dual q 24n, primal 20n, fused dual
-20n, fused primal 24n."""
+20n, fused primal 24n.
+--tv iso adds, in the same run and ahead of the anisotropic cases, PDHGRun(tv='iso') fused and unfused (the same model bytes and launch
+counts: only the arithmetic of the dual differs) and the two isotropic dual kernels alone; it writes profiles/pdhg/pdhg_iso_rates.json."""
 import argparse
 import json
 import os
@@ -44,7 +46,7 @@ def _case(N):
     return A, FirstDerivative2D(N, engine=A.engine), b
 
 
-def measure(N, steps, warmup):
+def measure(N, steps, warmup, tv="aniso"):
     from trips_py_amd.operators import operator_norm_sq
     from trips_py_amd.solvers import MMGKS, MRNSDRun, PDHGRun
     from trips_py_amd.solvers.PDHG import pdhg_steps
@@ -56,8 +58,11 @@ def measure(N, steps, warmup):
     lam = 0.01
     out = {"case": f"blur{N}_tv", "n": n, "rows_L": rows, "steps": steps, "warmup": warmup, "normK2_estimate": normK2}
     total = warmup + 3 * steps
-    for name, fused, model in (("pdhg_fused", True, 76 * n), ("pdhg_generic", False, 100 * n)):
-        run = PDHGRun(A, b, L, lam, sigma, tau, 0.0, np.inf, None, total, history=False, fused=fused)
+    cases = [("pdhg_fused", True, 76 * n, "aniso"), ("pdhg_generic", False, 100 * n, "aniso")]
+    if tv == "iso":                                     # the same bytes and launches: only the arithmetic of the dual differs
+        cases = [("pdhg_iso_fused", True, 76 * n, "iso"), ("pdhg_iso_unfused", False, 100 * n, "iso")] + cases
+    for name, fused, model, term in cases:
+        run = PDHGRun(A, b, L, lam, sigma, tau, 0.0, np.inf, None, total, history=False, fused=fused, tv=term)
         run.run(warmup)
         eng.synchronize()
         t = statistics.median(_window(lambda: run.run(steps), eng.synchronize) for _ in range(3))
@@ -79,6 +84,9 @@ def measure(N, steps, warmup):
         "k_pdhg_tv_primal": (16 * n + 4 * rows, lambda: eng.pdhg_tv_primal(L._h, tau, 0.0, np.inf, X0, run.z, run.q, X1, run.xbar, None,
                                                                         NP.ref(0), cap)),
     }
+    if tv == "iso":
+        kernels["k_pdhg_tv_dual_iso"] = (4 * n + 8 * rows, lambda: eng.pdhg_tv_dual_iso(L._h, sigma, lam, run.xbar, run.q, NP.ref(0), cap))
+        kernels["k_pdhg_dual_q_iso"] = (12 * rows, lambda: eng.pdhg_dual_q_iso(N, 1, sigma, lam, run.u, run.q, NP.ref(0), cap))
     for name, (nbytes, call) in kernels.items():
         def many():
             for _ in range(steps):
@@ -109,15 +117,18 @@ def measure(N, steps, warmup):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join("profiles", "pdhg", "pdhg_rates.json"))
+    ap.add_argument("--tv", choices=("aniso", "iso"), default="aniso")
+    ap.add_argument("--out", default=None)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--sizes", default="4096,512")
     a = ap.parse_args()
+    a.out = a.out or os.path.join("profiles", "pdhg", "pdhg_iso_rates.json" if a.tv == "iso" else "pdhg_rates.json")
     res = {"what": "PDHG iterations/s (PDHGRun.run, history off) fused and generic, model bytes over measured time, the new kernels alone, "
-                   "MRNSD and MMGKS for scale",
+                   "MRNSD and MMGKS for scale" + ("; isotropic TV fused and unfused and its two dual kernels from the same run"
+                                                   if a.tv == "iso" else ""),
            "device": torch.cuda.get_device_name(0), "protocol": "device events, warm-up, window closed by a synchronise, median of 3",
-           "entries": [measure(int(s), a.steps, a.warmup) for s in a.sizes.split(",")]}
+           "entries": [measure(int(s), a.steps, a.warmup, a.tv) for s in a.sizes.split(",")]}
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "w") as fh:
         json.dump(res, fh, indent=1)

@@ -272,6 +272,12 @@ SIGNATURES = {
                                    ctypes.POINTER(c_int), c_stream]),
     "trk_pdhg_iterate": (c_int, [c_op, c_op, c_int, c_int, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl, c_int, c_f32p, c_f32p, c_f32p, c_f32p,
                                  c_f32p, c_f32p, c_f32p, c_f32p, c_i64, c_int, c_f32p, c_f32p, c_f32p, c_f64p, c_int, c_stream]),
+    "trk_pdhg_blocks_iso": (c_int, [c_i64, c_i64, c_i64, c_int, c_int, c_op, ctypes.POINTER(c_int)]),
+    "trk_pdhg_dual_q_iso": (c_int, [c_int, c_int, c_i64, c_dbl, c_dbl, c_f32p, c_f32p, c_f64p, c_int, ctypes.POINTER(c_int), c_stream]),
+    "trk_pdhg_tv_dual_iso": (c_int, [c_op, c_dbl, c_dbl, c_f32p, c_f32p, c_f64p, c_int, ctypes.POINTER(c_int), c_stream]),
+    "trk_pdhg_iterate_iso": (c_int, [c_op, c_op, c_int, c_int, c_int, c_int, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl, c_int, c_f32p, c_f32p,
+                                     c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_i64, c_int, c_f32p, c_f32p, c_f32p, c_f64p, c_int,
+                                     c_stream]),
     "trk_gemv_t": (c_int, [c_f32p, c_i64, c_int, c_i64, c_f32p, c_f32p, c_f64p, c_stream]),
     "trk_gemv_t_x": (c_int, [c_f32p, c_i64, c_int, c_i64, c_f32p, c_f32p, c_f64p, c_f64p, c_stream]),
     "trk_gemv_t2": (c_int, [c_f32p, c_i64, c_int, c_i64, c_f32p, c_f32p, c_f64p, c_stream]),

@@ -4,6 +4,9 @@
 //   w = A xbar ;  p' = (p + sig (w - b)) / (1 + sig)
 //   u = L xbar ;  q' = clip(q + sig u, -lam, lam)
 //   z = A^T p' ;  v = L^T q' ;  x' = clip(x - tau (z + v), lo, hi) ;  xbar' = 2 x' - x
+// Isotropic TV (the *_iso entry points): lam sum_g ||(L x)_g||_2 with the groups of a geometry (N, frames) on the first-difference
+// row layout (include/trk.h); q' = every group of q + sig u projected onto the 2-norm ball of radius lam, everything else unchanged.
+// The grouped rows run on k_pdhg_dual_q_iso (tvops.hip: the column-thread layout), the tail rows on k_pdhg_dual_q below.
 // sig, tau, lam, lo, hi are host constants: nothing is read back inside the loop and trk_pdhg_iterate enqueues a whole solve.
 // The three streaming kernels are here; the fused forms for the 2-D first differences (no vector of the length of L xbar or L^T q
 // in memory) are in tvops.hip and share one entry (pdhg_internal.h).  Vectors fp32, sums fp64 block partials, no atomics: every
@@ -120,6 +123,61 @@ __global__ __launch_bounds__(NT) void k_pdhg_primal(int64_t n, float tau, float 
 
 inline bool finite_pos(double v) { return v > 0.0 && v < __builtin_inf(); }
 
+// the rows [H ; V] of `frames` N x N images: where the tail of an isotropic L begins
+inline int64_t iso_grouped_rows(int N, int frames) { return (int64_t)frames * 2 * N * (N - 1); }
+
+// The loop of trk_pdhg_iterate (N = 0: the l1 term, every row of L a group of its own) and of trk_pdhg_iterate_iso (N >= 2: the
+// isotropic groups of geometry (N, frames)).  Only the dual update of q differs.
+int pdhg_iterate(const char* who, trk_op* A, trk_op* L, int N, int frames, int k_first, int n_iters, double sigma, double tau, double lam,
+                 double lo, double hi, int fused, const float* b, float* p, float* q, float* w, float* u, float* z, float* v, float* X,
+                 int64_t x_ld, int keep_history, const float* x_prev, float* xbar, const float* x_true, double* NP,
+                 int np_capacity_blocks, trk_stream stream) {
+  const bool iso = N > 0;
+  TRK_REQUIRE(A && L && b && p && q && w && z && X && x_prev && xbar && NP, "%s: NULL argument", who);
+  TRK_REQUIRE(fused || (u && v), "%s: the generic path needs u and v", who);
+  TRK_REQUIRE(k_first >= 1 && n_iters >= 0, "%s: need k_first >= 1, n_iters >= 0", who);
+  TRK_REQUIRE(L->cols == A->cols, "%s: A and L must have the same number of columns", who);
+  const int64_t m = A->rows, n = A->cols, rows = L->rows;
+  int need = 0;
+  if (iso) {
+    TRK_REQUIRE(rows >= iso_grouped_rows(N, frames) && n == (int64_t)frames * N * N,
+                "%s: L is %lld x %lld, not the first differences of %d images of %d x %d (and a tail)", who, (long long)rows,
+                (long long)n, frames, N, N);
+    if (int rc = trk_pdhg_blocks_iso(m, n, rows, N, frames, fused ? L : nullptr, &need)) return rc;   // TRK_EUNSUPPORTED: no fused form
+    TRK_REQUIRE(!fused || (pdhg_tv_size(L) == N && frames == 1), "%s: the fused form takes the geometry of its handle, (%d, 1)", who,
+                pdhg_tv_size(L));
+  } else {
+    if (int rc = trk_pdhg_blocks(m, n, rows, fused ? L : nullptr, &need)) return rc;
+  }
+  TRK_REQUIRE(need <= np_capacity_blocks, "%s: partial buffer too small (%d blocks needed)", who, need);
+  for (int k = k_first; k < k_first + n_iters; ++k) {
+    double* part = NP + 8 * (int64_t)np_capacity_blocks * (k - 1);
+    float* x_new = X + (int64_t)(keep_history ? (k - 1) : ((k - 1) & 1)) * x_ld;
+    int nb = 0, rc;
+    if ((rc = trk_op_apply(A, 0, xbar, 0, w, 0, 1, nullptr, stream))) return rc;                       // w = A xbar
+    if ((rc = trk_pdhg_dual_p(m, sigma, w, b, p, part, np_capacity_blocks, &nb, stream))) return rc;
+    if (fused) {
+      rc = iso ? trk_pdhg_tv_dual_iso(L, sigma, lam, xbar, q, part, np_capacity_blocks, &nb, stream)
+               : trk_pdhg_tv_dual(L, sigma, lam, xbar, q, part, np_capacity_blocks, &nb, stream);
+    } else {
+      if ((rc = trk_op_apply(L, 0, xbar, 0, u, 0, 1, nullptr, stream))) return rc;                     // u = L xbar
+      rc = iso ? trk_pdhg_dual_q_iso(N, frames, rows, sigma, lam, u, q, part, np_capacity_blocks, &nb, stream)
+               : trk_pdhg_dual_q(rows, sigma, lam, u, q, part, np_capacity_blocks, &nb, stream);
+    }
+    if (rc) return rc;
+    if ((rc = trk_op_apply(A, 1, p, 0, z, 0, 1, nullptr, stream))) return rc;                          // z = A^T p'
+    if (fused) {
+      rc = trk_pdhg_tv_primal(L, tau, lo, hi, x_prev, z, q, x_new, xbar, x_true, part, np_capacity_blocks, &nb, stream);
+    } else {
+      if ((rc = trk_op_apply(L, 1, q, 0, v, 0, 1, nullptr, stream))) return rc;                        // v = L^T q'
+      rc = trk_pdhg_primal(n, tau, lo, hi, x_prev, z, v, x_new, xbar, x_true, part, np_capacity_blocks, &nb, stream);
+    }
+    if (rc) return rc;
+    x_prev = x_new;
+  }
+  return TRK_OK;
+}
+
 }  // namespace
 
 // ======================================================================================= C ABI
@@ -171,6 +229,45 @@ int trk_pdhg_dual_q(int64_t rows, double sigma, double lam, const float* u, floa
   return TRK_OK;
 }
 
+int trk_pdhg_blocks_iso(int64_t m, int64_t n, int64_t rows, int N, int frames, const trk_op* L_fused, int* blocks) {
+  TRK_REQUIRE(blocks && m >= 1 && n >= 1 && rows >= 1, "trk_pdhg_blocks_iso: need m, n, rows >= 1");
+  TRK_REQUIRE(N >= 2 && frames >= 1 && frames <= 65535, "trk_pdhg_blocks_iso: need N >= 2, 1 <= frames <= 65535");
+  const int64_t off = iso_grouped_rows(N, frames);
+  TRK_REQUIRE(rows >= off, "trk_pdhg_blocks_iso: %lld rows are fewer than the %lld of %d images of %d x %d", (long long)rows,
+              (long long)off, frames, N, N);
+  int g = stream_grid(m > n ? m : n), t;
+  if (L_fused) {
+    t = pdhg_tv_blocks(L_fused);
+    if (t == 0) return fail(TRK_EUNSUPPORTED, "trk_pdhg_blocks_iso: the fused forms take a handle from trk_deriv2d_create only");
+  } else {
+    t = pdhg_iso_blocks(N, frames) + (rows > off ? stream_grid(rows - off) : 0);      // grouped rows, then the tail's
+  }
+  *blocks = t > g ? t : g;
+  return TRK_OK;
+}
+
+int trk_pdhg_dual_q_iso(int N, int frames, int64_t rows, double sigma, double lam, const float* u, float* q, double* partials,
+                        int capacity_blocks, int* n_blocks, trk_stream st) {
+  TRK_REQUIRE(u && q && partials && n_blocks, "trk_pdhg_dual_q_iso: NULL argument");
+  TRK_REQUIRE(N >= 2 && frames >= 1 && frames <= 65535, "trk_pdhg_dual_q_iso: need N >= 2, 1 <= frames <= 65535");
+  const int64_t off = iso_grouped_rows(N, frames);
+  TRK_REQUIRE(rows >= off, "trk_pdhg_dual_q_iso: %lld rows are fewer than the %lld of %d images of %d x %d", (long long)rows,
+              (long long)off, frames, N, N);
+  TRK_REQUIRE(finite_pos(sigma), "trk_pdhg_dual_q_iso: sigma must be finite and > 0");
+  TRK_REQUIRE(lam >= 0.0 && lam < __builtin_inf(), "trk_pdhg_dual_q_iso: lam must be finite and >= 0");
+  TRK_REQUIRE(q != u, "trk_pdhg_dual_q_iso: q must not alias u");
+  const int grouped = pdhg_iso_blocks(N, frames), tail = rows > off ? stream_grid(rows - off) : 0;
+  TRK_REQUIRE(grouped + tail <= capacity_blocks, "trk_pdhg_dual_q_iso: partial buffer too small (%d blocks needed)", grouped + tail);
+  *n_blocks = grouped + tail;
+  pdhg_dual_q_iso_launch(N, frames, (float)sigma, (float)lam, u, q, partials, (hipStream_t)st);
+  TRK_LAUNCH_CHECK();
+  if (tail) {   // groups of one: the streaming kernel on the slices, its blocks' rows of partials behind the grouped kernel's
+    int nt = 0;
+    return trk_pdhg_dual_q(rows - off, sigma, lam, u + off, q + off, partials + 8 * (int64_t)grouped, capacity_blocks - grouped, &nt, st);
+  }
+  return TRK_OK;
+}
+
 int trk_pdhg_primal(int64_t n, double tau, double lo, double hi, const float* x, const float* z, const float* v, float* x_new,
                     float* xbar, const float* x_true, double* partials, int capacity_blocks, int* n_blocks, trk_stream st) {
   TRK_REQUIRE(x && z && x_new && xbar && partials && n_blocks, "trk_pdhg_primal: NULL argument");
@@ -197,37 +294,17 @@ int trk_pdhg_iterate(trk_op* A, trk_op* L, int k_first, int n_iters, double sigm
                      int fused, const float* b, float* p, float* q, float* w, float* u, float* z, float* v, float* X, int64_t x_ld,
                      int keep_history, const float* x_prev, float* xbar, const float* x_true, double* NP, int np_capacity_blocks,
                      trk_stream stream) {
-  TRK_REQUIRE(A && L && b && p && q && w && z && X && x_prev && xbar && NP, "trk_pdhg_iterate: NULL argument");
-  TRK_REQUIRE(fused || (u && v), "trk_pdhg_iterate: the generic path needs u and v");
-  TRK_REQUIRE(k_first >= 1 && n_iters >= 0, "trk_pdhg_iterate: need k_first >= 1, n_iters >= 0");
-  TRK_REQUIRE(L->cols == A->cols, "trk_pdhg_iterate: A and L must have the same number of columns");
-  const int64_t m = A->rows, n = A->cols, rows = L->rows;
-  int need = 0;
-  if (int rc = trk_pdhg_blocks(m, n, rows, fused ? L : nullptr, &need)) return rc;
-  TRK_REQUIRE(need <= np_capacity_blocks, "trk_pdhg_iterate: partial buffer too small (%d blocks needed)", need);
-  for (int k = k_first; k < k_first + n_iters; ++k) {
-    double* part = NP + 8 * (int64_t)np_capacity_blocks * (k - 1);
-    float* x_new = X + (int64_t)(keep_history ? (k - 1) : ((k - 1) & 1)) * x_ld;
-    int nb = 0, rc;
-    if ((rc = trk_op_apply(A, 0, xbar, 0, w, 0, 1, nullptr, stream))) return rc;                       // w = A xbar
-    if ((rc = trk_pdhg_dual_p(m, sigma, w, b, p, part, np_capacity_blocks, &nb, stream))) return rc;
-    if (fused) {
-      if ((rc = trk_pdhg_tv_dual(L, sigma, lam, xbar, q, part, np_capacity_blocks, &nb, stream))) return rc;
-    } else {
-      if ((rc = trk_op_apply(L, 0, xbar, 0, u, 0, 1, nullptr, stream))) return rc;                     // u = L xbar
-      if ((rc = trk_pdhg_dual_q(rows, sigma, lam, u, q, part, np_capacity_blocks, &nb, stream))) return rc;
-    }
-    if ((rc = trk_op_apply(A, 1, p, 0, z, 0, 1, nullptr, stream))) return rc;                          // z = A^T p'
-    if (fused) {
-      rc = trk_pdhg_tv_primal(L, tau, lo, hi, x_prev, z, q, x_new, xbar, x_true, part, np_capacity_blocks, &nb, stream);
-    } else {
-      if ((rc = trk_op_apply(L, 1, q, 0, v, 0, 1, nullptr, stream))) return rc;                        // v = L^T q'
-      rc = trk_pdhg_primal(n, tau, lo, hi, x_prev, z, v, x_new, xbar, x_true, part, np_capacity_blocks, &nb, stream);
-    }
-    if (rc) return rc;
-    x_prev = x_new;
-  }
-  return TRK_OK;
+  return pdhg_iterate("trk_pdhg_iterate", A, L, 0, 0, k_first, n_iters, sigma, tau, lam, lo, hi, fused, b, p, q, w, u, z, v, X, x_ld,
+                      keep_history, x_prev, xbar, x_true, NP, np_capacity_blocks, stream);
+}
+
+int trk_pdhg_iterate_iso(trk_op* A, trk_op* L, int N, int frames, int k_first, int n_iters, double sigma, double tau, double lam,
+                         double lo, double hi, int fused, const float* b, float* p, float* q, float* w, float* u, float* z, float* v,
+                         float* X, int64_t x_ld, int keep_history, const float* x_prev, float* xbar, const float* x_true, double* NP,
+                         int np_capacity_blocks, trk_stream stream) {
+  TRK_REQUIRE(N >= 2 && frames >= 1, "trk_pdhg_iterate_iso: need N >= 2, frames >= 1");
+  return pdhg_iterate("trk_pdhg_iterate_iso", A, L, N, frames, k_first, n_iters, sigma, tau, lam, lo, hi, fused, b, p, q, w, u, z, v, X,
+                      x_ld, keep_history, x_prev, xbar, x_true, NP, np_capacity_blocks, stream);
 }
 
 }  // extern "C"

@@ -28,6 +28,28 @@ __device__ __forceinline__ float pdhg_q_entry(float sig, float lam, float u, flo
   return qn;
 }
 
+// dual of the regulariser, isotropic: the H and V entry of one pixel are projected together onto the 2-norm ball of radius lam.
+//   th = fmaf(sig, uh, qh) ; tv = fmaf(sig, uv, qv) ; m = sqrtf(fmaf(th, th, tv * tv))
+//   m <= lam: q' = t ; else s = lam / m, q' = t * s          (lam = 0: m = 0 keeps t = 0, m > 0 gives s = 0)
+//   s1 += sqrt(uh^2 + uv^2) ; s3 += (qh' - qh)^2 + (qv' - qv)^2     (fp64 from the fp32 values)
+// sqrtf and / are the correctly rounded ones (no fast-math): a host restatement with the same operations has the same bits.
+__device__ __forceinline__ void pdhg_q_pair(float sig, float lam, float uh, float uv, float& qh, float& qv, double& s1, double& s3) {
+#pragma clang fp contract(off)
+  const float th = fmaf(sig, uh, qh), tv = fmaf(sig, uv, qv);
+  const float m = sqrtf(fmaf(th, th, tv * tv));
+  float nh = th, nv = tv;
+  if (!(m <= lam)) {
+    const float s = lam / m;
+    nh = th * s;
+    nv = tv * s;
+  }
+  const double dh = (double)nh - (double)qh, dv = (double)nv - (double)qv;
+  s1 += sqrt((double)uh * (double)uh + (double)uv * (double)uv);
+  s3 += dh * dh + dv * dv;
+  qh = nh;
+  qv = nv;
+}
+
 // primal: g = z + v (formed by the caller) ; x' = clip(fmaf(-tau, g, x), lo, hi) ; xbar' = fmaf(2, x', -x) ; d = x' - x
 // s4 += x'^2, s5 += d^2, s6 += (x' - x_true)^2, s7 += 1 where x' sits on a bound
 template <bool HAS_XT>
@@ -48,5 +70,12 @@ __device__ __forceinline__ void pdhg_x_entry(float tau, float lo, float hi, floa
 
 // tvops.hip: the blocks (= rows of 8 partials) of the fused forms on a 2-D first-difference handle, 0 for any other handle
 int pdhg_tv_blocks(const trk_op* L);
+// tvops.hip: N of a 2-D first-difference handle, 0 for any other handle
+int pdhg_tv_size(const trk_op* L);
+// tvops.hip: the grouped part of the unfused isotropic dual — `frames` blocks of [H ; V] rows of an N x N image in u and q, pairs
+// through pdhg_q_pair, the last row's H and the last column's V through pdhg_q_entry.  pdhg_iso_blocks: the rows of partials it
+// writes (slots 1 and 3 of rows 0 .. blocks - 1).
+int pdhg_iso_blocks(int N, int frames);
+void pdhg_dual_q_iso_launch(int N, int frames, float sig, float lam, const float* u, float* q, double* partials, hipStream_t s);
 
 }  // namespace trk

@@ -318,9 +318,29 @@ __global__ __launch_bounds__(NT) void k_time_fwd(const float* __restrict__ x, fl
 // Fused forms for PDHG (pdhg.hip; the entries: pdhg_internal.h), nothing of the length of L2 xbar or L2^T q touches memory:
 //   k_pdhg_tv_dual:    q' = clip(q + sig L2 xbar, -lam, lam), the differences formed in registers as k_d2_fwd forms them
 //                      (xbar read: 4n; q read and written: 8n + 8n); partials 1 (sum |L2 xbar|) and 3 (||q' - q||^2) of the block's row
+//                      <true>: isotropic TV, (H[i][j], V[i][j]) projected onto the 2-norm ball instead (partial 1: the sum of the
+//                      groups' 2-norms); the same bytes.  k_pdhg_dual_q_iso: that projection on a stored u = L xbar.
 //   k_pdhg_tv_primal:  x' = clip(x - tau (z + L2^T q), lo, hi), xbar' = 2 x' - x, L2^T q gathered in the order of k_d2_adj
 //                      (x, z, q read: 16n; x', xbar' written: 8n); partials 4 to 7
 // One thread per image column over batches of RB rows, as the stencils above; every thread stays to the block sums.
+//
+// One pixel's rows of the isotropic duals: the thread of column j holds both members of pixel (i, j)'s group.  pair: both exist
+// (i < N - 1 and j < N - 1), projected together; the last row's H and the last column's V are groups of one: the clip.
+__device__ __forceinline__ void pdhg_iso_pixel(bool has_h, bool has_v, float sig, float lam, float uh, float uv, float ph, float pv,
+                                               float* dh, float* dv, double& s1, double& s3) {
+  if (has_h && has_v) {
+    pdhg_q_pair(sig, lam, uh, uv, ph, pv, s1, s3);
+    *dh = ph;
+    *dv = pv;
+  } else if (has_h) {
+    *dh = pdhg_q_entry(sig, lam, uh, ph, s1, s3);
+  } else if (has_v) {
+    *dv = pdhg_q_entry(sig, lam, uv, pv, s1, s3);
+  }
+}
+
+// ISO: the isotropic dual (k_pdhg_tv_dual_iso of the documents), the same loads and stores, the H and V entry of a pixel joined.
+template <bool ISO>
 __global__ __launch_bounds__(NT) void k_pdhg_tv_dual(const float* __restrict__ xbar, float* q, int N, float sig, float lam,
                                                      double* __restrict__ partials) {
   __shared__ double red[NT / 64];
@@ -347,8 +367,13 @@ __global__ __launch_bounds__(NT) void k_pdhg_tv_dual(const float* __restrict__ x
       for (int t = 0; t < RB; ++t) {
         const int i = i0 + t;
         if (i < N) {
-          if (hr) qh[h0 + (int64_t)t * (N - 1)] = pdhg_q_entry(sig, lam, xc[t] - xr[t], ph[t], s1, s3);
-          if (i < N - 1) qv[o0 + (int64_t)t * N] = pdhg_q_entry(sig, lam, xc[t] - xc[t + 1], pv[t], s1, s3);
+          if (ISO) {
+            pdhg_iso_pixel(hr, i < N - 1, sig, lam, xc[t] - xr[t], xc[t] - xc[t + 1], ph[t], pv[t], qh + h0 + (int64_t)t * (N - 1),
+                           qv + o0 + (int64_t)t * N, s1, s3);
+          } else {
+            if (hr) qh[h0 + (int64_t)t * (N - 1)] = pdhg_q_entry(sig, lam, xc[t] - xr[t], ph[t], s1, s3);
+            if (i < N - 1) qv[o0 + (int64_t)t * N] = pdhg_q_entry(sig, lam, xc[t] - xc[t + 1], pv[t], s1, s3);
+          }
         }
       }
     }
@@ -357,6 +382,50 @@ __global__ __launch_bounds__(NT) void k_pdhg_tv_dual(const float* __restrict__ x
   s3 = block_sum<NT>(s3, red);
   if (threadIdx.x == 0) {
     const size_t blk = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
+    partials[blk * 8 + 1] = s1;
+    partials[blk * 8 + 3] = s3;
+  }
+}
+
+// The unfused isotropic dual on u = L xbar in memory: `frames` blocks of [H ; V] rows (blockIdx.z = frame), the column-thread layout
+// of k_pdhg_tv_dual with u read where that kernel forms the differences.  Partials 1 and 3 of row (z gridDim.y + y) gridDim.x + x.
+__global__ __launch_bounds__(NT) void k_pdhg_dual_q_iso(const float* __restrict__ u, float* q, int N, float sig, float lam,
+                                                        double* __restrict__ partials) {
+  __shared__ double red[NT / 64];
+  const int64_t frame = (int64_t)blockIdx.z * 2 * N * (N - 1);
+  const float* __restrict__ uh = u + frame;
+  const float* __restrict__ uv = uh + (int64_t)N * (N - 1);
+  float* qh = q + frame;
+  float* qv = qh + (int64_t)N * (N - 1);
+  const int j = blockIdx.x * NT + threadIdx.x;
+  double s1 = 0.0, s3 = 0.0;
+  if (j < N) {
+    const bool hr = j < N - 1;
+    for (int i0 = blockIdx.y * RB; i0 < N; i0 += gridDim.y * RB) {
+      const int64_t o0 = (int64_t)i0 * N + j;
+      const int64_t h0 = (int64_t)i0 * (N - 1) + j;
+      float ah[RB], av[RB], ph[RB], pv[RB];
+#pragma unroll
+      for (int t = 0; t < RB; ++t) {
+        const bool in = i0 + t < N;
+        ah[t] = (hr && in) ? uh[h0 + (int64_t)t * (N - 1)] : 0.f;
+        ph[t] = (hr && in) ? qh[h0 + (int64_t)t * (N - 1)] : 0.f;
+        av[t] = (i0 + t < N - 1) ? uv[o0 + (int64_t)t * N] : 0.f;
+        pv[t] = (i0 + t < N - 1) ? qv[o0 + (int64_t)t * N] : 0.f;
+      }
+#pragma unroll
+      for (int t = 0; t < RB; ++t) {
+        const int i = i0 + t;
+        if (i < N)
+          pdhg_iso_pixel(hr, i < N - 1, sig, lam, ah[t], av[t], ph[t], pv[t], qh + h0 + (int64_t)t * (N - 1), qv + o0 + (int64_t)t * N,
+                         s1, s3);
+      }
+    }
+  }
+  s1 = block_sum<NT>(s1, red);
+  s3 = block_sum<NT>(s3, red);
+  if (threadIdx.x == 0) {
+    const size_t blk = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
     partials[blk * 8 + 1] = s1;
     partials[blk * 8 + 3] = s3;
   }
@@ -665,7 +734,23 @@ int trk_pdhg_tv_dual(trk_op* L, double sigma, double lam, const float* xbar, flo
   const Grid2 g2 = grid2(N, 1, true);
   TRK_REQUIRE(g2.per_frame <= capacity_blocks, "trk_pdhg_tv_dual: partial buffer too small (%d blocks needed)", g2.per_frame);
   *n_blocks = g2.per_frame;
-  hipLaunchKernelGGL(k_pdhg_tv_dual, g2.g, dim3(NT), 0, (hipStream_t)st, xbar, q, N, (float)sigma, (float)lam, partials);
+  hipLaunchKernelGGL(k_pdhg_tv_dual<false>, g2.g, dim3(NT), 0, (hipStream_t)st, xbar, q, N, (float)sigma, (float)lam, partials);
+  TRK_LAUNCH_CHECK();
+  return TRK_OK;
+}
+
+int trk_pdhg_tv_dual_iso(trk_op* L, double sigma, double lam, const float* xbar, float* q, double* partials, int capacity_blocks,
+                         int* n_blocks, trk_stream st) {
+  TRK_REQUIRE(L && xbar && q && partials && n_blocks, "trk_pdhg_tv_dual_iso: NULL argument");
+  if (L->kind != 3) return fail(TRK_EUNSUPPORTED, "trk_pdhg_tv_dual_iso: the fused forms take a handle from trk_deriv2d_create only");
+  TRK_REQUIRE(sigma > 0.0 && sigma < __builtin_inf(), "trk_pdhg_tv_dual_iso: sigma must be finite and > 0");
+  TRK_REQUIRE(lam >= 0.0 && lam < __builtin_inf(), "trk_pdhg_tv_dual_iso: lam must be finite and >= 0");
+  TRK_REQUIRE(q != xbar, "trk_pdhg_tv_dual_iso: q must not alias xbar");
+  const int N = static_cast<D2Impl*>(L->impl)->N;
+  const Grid2 g2 = grid2(N, 1, true);
+  TRK_REQUIRE(g2.per_frame <= capacity_blocks, "trk_pdhg_tv_dual_iso: partial buffer too small (%d blocks needed)", g2.per_frame);
+  *n_blocks = g2.per_frame;
+  hipLaunchKernelGGL(k_pdhg_tv_dual<true>, g2.g, dim3(NT), 0, (hipStream_t)st, xbar, q, N, (float)sigma, (float)lam, partials);
   TRK_LAUNCH_CHECK();
   return TRK_OK;
 }
@@ -693,3 +778,8 @@ int trk_pdhg_tv_primal(trk_op* L, double tau, double lo, double hi, const float*
 }  // extern "C"
 
 int trk::pdhg_tv_blocks(const trk_op* L) { return (L && L->kind == 3) ? grid2(static_cast<D2Impl*>(L->impl)->N, 1, true).per_frame : 0; }
+int trk::pdhg_tv_size(const trk_op* L) { return (L && L->kind == 3) ? static_cast<D2Impl*>(L->impl)->N : 0; }
+int trk::pdhg_iso_blocks(int N, int frames) { return grid2(N, 1, true).per_frame * frames; }
+void trk::pdhg_dual_q_iso_launch(int N, int frames, float sig, float lam, const float* u, float* q, double* partials, hipStream_t s) {
+  hipLaunchKernelGGL(k_pdhg_dual_q_iso, grid2(N, frames, true).g, dim3(NT), 0, s, u, q, N, sig, lam, partials);
+}

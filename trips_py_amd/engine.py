@@ -775,6 +775,42 @@ class HipEngine:
                                        None if x_true is None else x_true.data_ptr(), _ptr(NP), int(np_cap), self.stream())
         _lib.check(rc, "trk_pdhg_iterate")
 
+    # isotropic TV: the groups of geometry (N, frames) on the first-difference row layout (include/trk.h)
+    def pdhg_blocks_iso(self, m, n, rows, N, frames, fused_handle=None):
+        """pdhg_blocks for the isotropic forms."""
+        c = ctypes.c_int(0)
+        _lib.check(self.lib.trk_pdhg_blocks_iso(int(m), int(n), int(rows), int(N), int(frames), fused_handle, ctypes.byref(c)),
+                   "trk_pdhg_blocks_iso")
+        return c.value
+
+    def pdhg_dual_q_iso(self, N, frames, sigma, lam, u, q, partials, capacity):
+        """q = each group of q + sigma u projected onto the 2-norm ball of radius lam, in place; slots 1, 3.  Returns the rows of
+        partials that wrote (the grouped kernel's, then the tail's)."""
+        c = ctypes.c_int(0)
+        rc = self.lib.trk_pdhg_dual_q_iso(int(N), int(frames), q.numel(), float(sigma), float(lam), u.data_ptr(), q.data_ptr(),
+                                          _ptr(partials), int(capacity), ctypes.byref(c), self.stream())
+        _lib.check(rc, "trk_pdhg_dual_q_iso")
+        return c.value
+
+    def pdhg_tv_dual_iso(self, handle, sigma, lam, xbar, q, partials, capacity):
+        """pdhg_dual_q_iso with u = L xbar formed in registers (a FirstDerivative2D handle: geometry (N, 1))."""
+        c = ctypes.c_int(0)
+        rc = self.lib.trk_pdhg_tv_dual_iso(handle, float(sigma), float(lam), xbar.data_ptr(), q.data_ptr(), _ptr(partials),
+                                           int(capacity), ctypes.byref(c), self.stream())
+        _lib.check(rc, "trk_pdhg_tv_dual_iso")
+        return c.value
+
+    def pdhg_iterate_iso(self, hA, hL, N, frames, k_first, n_iters, sigma, tau, lam, lo, hi, fused, b, p, q, w, u, z, v, X, keep, x_prev,
+                         xbar, x_true, NP, np_cap):
+        """pdhg_iterate with the isotropic dual of geometry (N, frames)."""
+        rc = self.lib.trk_pdhg_iterate_iso(hA, hL, int(N), int(frames), int(k_first), int(n_iters), float(sigma), float(tau), float(lam),
+                                           float(lo), float(hi), int(bool(fused)), b.data_ptr(), p.data_ptr(), q.data_ptr(),
+                                           w.data_ptr(), None if u is None else u.data_ptr(), z.data_ptr(),
+                                           None if v is None else v.data_ptr(), X.data_ptr(), X.stride(0), int(bool(keep)),
+                                           x_prev.data_ptr(), xbar.data_ptr(), None if x_true is None else x_true.data_ptr(), _ptr(NP),
+                                           int(np_cap), self.stream())
+        _lib.check(rc, "trk_pdhg_iterate_iso")
+
     def finalize_batched(self, partials, nblocks, nvals, batches, out, out_stride):
         rc = self.lib.trk_finalize_batched(_ptr(partials), int(nblocks), int(nvals), int(batches), _ptr(out), int(out_stride),
                                            self.stream())

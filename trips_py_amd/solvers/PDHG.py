@@ -1,15 +1,20 @@
 """PDHG on the HIP engine: min_x 1/2 ||A x - b||^2 + lam ||L x||_1 subject to lower <= x <= upper — the exact l1 / anisotropic TV term
 and a box in one solve, by the primal-dual hybrid gradient iteration (Chambolle and Pock 2011, algorithm 1, theta = 1; CIL's PDHG).
+With tv='iso' the term is lam sum_g ||(L x)_g||_2, isotropic TV (Rudin, Osher and Fatemi): the horizontal and the vertical difference
+of a pixel form one group, every other row of L a group of its own (include/trk.h: the groups of a geometry (N, frames)).
 
 With K = [A; L], duals p and q (zero at the start), x_0 the caller's start projected onto the box and xbar_0 = x_0, per iteration:
     w = A xbar ; p = (p + sigma (w - b)) / (1 + sigma)                      (trk_pdhg_dual_p)
     u = L xbar ; q = clip(q + sigma u, -lam, lam)                           (trk_pdhg_dual_q, or trk_pdhg_tv_dual: u in registers)
+                 tv='iso': q = each group of q + sigma u projected onto the 2-norm ball of radius lam
+                                                                            (trk_pdhg_dual_q_iso, or trk_pdhg_tv_dual_iso)
     z = A^T p ; v = L^T q ; x = clip(x - tau (z + v), lower, upper) ; xbar = 2 x - x_previous
                                                                             (trk_pdhg_primal, or trk_pdhg_tv_primal: v gathered)
 sigma, tau and lam are host constants, so nothing is read back inside the loop: a whole solve is one enqueue (trk_pdhg_iterate).
 Vectors are fp32, the reported sums fp64 (include/trk.h: the operations and the layout of S).  It converges for
 sigma tau ||K||^2 < 1.
-Not built: isotropic TV, fused forms for SpaceTimeDerivative / Framelet2D (they run on the generic path), sharded PDHG, diagonal
+Not built: three-member groups (h, v, t) for fully isotropic space-time TV (SpaceTimeDerivative is spatially isotropic, temporally
+l1), rectangular images, fused forms for SpaceTimeDerivative / Framelet2D (they run on the generic path), sharded PDHG, diagonal
 preconditioning or adaptive step balancing (`ratio` is the only knob), other data terms.
 """
 import numpy as np
@@ -20,15 +25,48 @@ from .CGLS import _row_of
 from .MRNSD import MRNSDRun, _host
 
 
+def _iso_geometry(L, tv, tv_dims):
+    """None for tv='aniso'; for 'iso' (N, frames) of the isotropic groups on L's rows: the operator's own, or the caller's tv_dims,
+    checked against L.shape."""
+    from ..operators import FirstDerivative2D, SpaceTimeDerivative
+    if tv not in ("aniso", "iso"):
+        raise ValueError(f"PDHG: tv must be 'aniso' or 'iso', not {tv!r}")
+    if tv == "aniso":
+        if tv_dims is not None:
+            raise ValueError("PDHG: tv_dims belongs to tv='iso'")
+        return None
+    if tv_dims is not None:
+        try:
+            N, frames = (int(d) for d in tv_dims)
+        except (TypeError, ValueError):
+            raise ValueError("PDHG: tv_dims must be (N, frames)") from None
+    elif isinstance(L, FirstDerivative2D):
+        N, frames = L.N, 1
+    elif isinstance(L, SpaceTimeDerivative):
+        N, frames = L.N, L.nt_global
+    else:
+        raise ValueError(f"PDHG: tv='iso' needs tv_dims=(N, frames) for a {type(L).__name__} regulariser: only FirstDerivative2D and "
+                         "SpaceTimeDerivative carry the geometry of their rows")
+    if N < 2 or frames < 1:
+        raise ValueError("PDHG: tv_dims needs N >= 2 and frames >= 1")
+    rows, cols = L.shape
+    if rows < frames * 2 * N * (N - 1) or cols != frames * N * N:
+        raise ValueError(f"PDHG: L is {rows} x {cols}, not the first differences of {frames} images of {N} x {N} (and a tail of further rows)")
+    return N, frames
+
+
 class PDHGRun:
     """The PDHG iteration as an object, like MRNSDRun: `step()` enqueues one iteration from Python, `run(n)` n of them in one library
     call when A and L both have handles (trk_pdhg_iterate: the same kernels, the same bits), `rows()` / `row(k)` download the sums.
 
     Row k (1-based) at S + 8k = [||A xbar - b||^2, sum |L xbar|, ||p_k - p_{k-1}||^2, ||q_k - q_{k-1}||^2, ||x_k||^2,
     ||x_k - x_{k-1}||^2, ||x_k - x_true||^2, entries of x_k on a bound], the first two at xbar_{k-1} = 2 x_{k-1} - x_{k-2}: the point
-    iteration k applies A and L to.  `fused`: None = the fused first-difference kernels where L takes them, True / False forces."""
+    iteration k applies A and L to.  `fused`: None = the fused first-difference kernels where L takes them, True / False forces.
+    tv='iso': the isotropic term — sum |L xbar| becomes the sum of the groups' 2-norms; the geometry (N, frames) is
+    FirstDerivative2D's (N, 1), SpaceTimeDerivative's (N, nt) or, for any other operator with that row layout, `tv_dims`."""
 
-    def __init__(self, A, b, L, lam, sigma, tau, lower, upper, x0, max_iter, x_true=None, history=True, fused=None):
+    def __init__(self, A, b, L, lam, sigma, tau, lower, upper, x0, max_iter, x_true=None, history=True, fused=None, tv="aniso",
+                 tv_dims=None):
         self.A = A = as_operator(A)
         self.L = L = as_operator(L, "L")
         self.eng = eng = A.engine
@@ -46,10 +84,14 @@ class PDHGRun:
             raise ValueError("PDHG: sigma and tau must be finite and > 0")
         if not self.lo <= self.hi:
             raise ValueError("PDHG: need lower <= upper")
+        self.tv = tv
+        self.geo = _iso_geometry(L, tv, tv_dims)
         self.max_iter = max_iter = int(max_iter)
         self.bv = eng.to_vec(b, m)
         self.xt = None if x_true is None else eng.to_vec(x_true, n)
         can = bool(hasattr(L, "_h") and hasattr(eng, "pdhg_fused_caps") and eng.pdhg_fused_caps(L._h))
+        if self.geo is not None:                                   # the fused isotropic dual pairs the rows as its handle lays them out
+            can = can and self.geo == (L.N, 1)
         if fused and not can:
             raise ValueError("PDHG: fused=True needs a FirstDerivative2D regulariser on the HIP engine")
         self.fused = can if fused is None else bool(fused)
@@ -64,7 +106,10 @@ class PDHGRun:
         self.p, self.w = eng.zeros(m), eng.empty(m)
         self.q, self.z = eng.zeros(rows), eng.empty(n)
         self.u, self.v = (None, None) if self.fused else (eng.empty(rows), eng.empty(n))
-        self.cap = eng.pdhg_blocks(m, n, rows, L._h if self.fused else None)
+        if self.geo is None:
+            self.cap = eng.pdhg_blocks(m, n, rows, L._h if self.fused else None)
+        else:
+            self.cap = eng.pdhg_blocks_iso(m, n, rows, *self.geo, L._h if self.fused else None)
         self.NP = eng.scalars(8 * self.cap * max(1, max_iter))     # zeroed: a kernel writes only its slots of its blocks' rows
         self.S = eng.scalars(8 * (max_iter + 1))
         self.B = eng.scalars(1)                                    # ||b||^2
@@ -85,10 +130,11 @@ class PDHGRun:
         A.apply(self.xbar, out=self.w)
         eng.pdhg_dual_p(self.sigma, self.w, self.bv, self.p, part, self.cap)
         if self.fused:
-            eng.pdhg_tv_dual(L._h, self.sigma, self.lam, self.xbar, self.q, part, self.cap)
+            dual = eng.pdhg_tv_dual if self.geo is None else eng.pdhg_tv_dual_iso
+            dual(L._h, self.sigma, self.lam, self.xbar, self.q, part, self.cap)
         else:
             L.apply(self.xbar, out=self.u)
-            eng.pdhg_dual_q(self.sigma, self.lam, self.u, self.q, part, self.cap)
+            self._dual_q(self.u, self.q, part)
         A.apply(self.p, out=self.z, transpose=True)
         if self.fused:
             eng.pdhg_tv_primal(L._h, self.tau, self.lo, self.hi, self.x_cur, self.z, self.q, x_new, self.xbar, self.xt, part, self.cap)
@@ -98,6 +144,12 @@ class PDHGRun:
         self.x_cur = x_new
         self.hist.pushed(k - 1)
 
+    def _dual_q(self, u, q, part):
+        if self.geo is None:
+            self.eng.pdhg_dual_q(self.sigma, self.lam, u, q, part, self.cap)
+        else:
+            self.eng.pdhg_dual_q_iso(*self.geo, self.sigma, self.lam, u, q, part, self.cap)
+
     _run_c_loop = MRNSDRun._run_c_loop                 # the chunking of a streamed history: CGLSRun's
 
     def run(self, n_steps):
@@ -106,11 +158,14 @@ class PDHGRun:
         if n_steps <= 0:
             return
         eng = self.eng
-        if hasattr(self.A, "_h") and hasattr(self.L, "_h") and hasattr(eng, "pdhg_iterate"):
+        if hasattr(self.A, "_h") and hasattr(self.L, "_h") and hasattr(eng, "pdhg_iterate" if self.geo is None else "pdhg_iterate_iso"):
             def call(k_first, n, X, keep):
-                eng.pdhg_iterate(self.A._h, self.L._h, k_first, n, self.sigma, self.tau, self.lam, self.lo, self.hi, self.fused, self.bv,
-                                 self.p, self.q, self.w, self.u, self.z, self.v, X, keep, self.x_cur, self.xbar, self.xt,
-                                 self.NP.ref(0), self.cap)
+                rest = (k_first, n, self.sigma, self.tau, self.lam, self.lo, self.hi, self.fused, self.bv, self.p, self.q, self.w, self.u,
+                        self.z, self.v, X, keep, self.x_cur, self.xbar, self.xt, self.NP.ref(0), self.cap)
+                if self.geo is None:
+                    eng.pdhg_iterate(self.A._h, self.L._h, *rest)
+                else:
+                    eng.pdhg_iterate_iso(self.A._h, self.L._h, *self.geo, *rest)
                 self.x_cur = _row_of(X, k_first + n - 2, keep)
             self._run_c_loop(n_steps, call)
         else:
@@ -139,13 +194,13 @@ class PDHGRun:
         return float(np.sqrt(self.B.host(0, 1)[0]))
 
     def objective_at(self, x):
-        """1/2 ||A x - b||^2 + lam ||L x||_1 at a device vector x, from one pair of products (the sums of the dual kernels on scratch
-        duals; the state of the run is left alone)."""
+        """1/2 ||A x - b||^2 + lam ||L x||_1 (tv='iso': lam sum_g ||(L x)_g||_2) at a device vector x, from one pair of products (the
+        sums of the dual kernels on scratch duals; the state of the run is left alone)."""
         eng = self.eng
         w, u = self.A.apply(x), self.L.apply(x)
         part, out = eng.scalars(8 * self.cap), eng.scalars(8)
         eng.pdhg_dual_p(self.sigma, w, self.bv, eng.zeros(w.numel()), part.ref(0), self.cap)
-        eng.pdhg_dual_q(self.sigma, self.lam, u, eng.zeros(u.numel()), part.ref(0), self.cap)
+        self._dual_q(u, eng.zeros(u.numel()), part.ref(0))
         eng.finalize_batched(part.ref(0), self.cap, 8, 1, out.ref(0), 8)
         s = out.host()
         return 0.5 * float(s[0]) + self.lam * float(s[1])
@@ -158,10 +213,16 @@ def pdhg_steps(normK2, ratio=1.0):
 
 
 def PDHG(A, b, L, lam, max_iter, tol=0, x0=None, x_true=None, lower=0.0, upper=np.inf, sigma=None, tau=None, normK2=None, ratio=1.0,
-         **kwargs):
+         tv="aniso", tv_dims=None, **kwargs):
     """Primal-dual hybrid gradient: min 1/2 ||A x - b||^2 + lam ||L x||_1 subject to lower <= x <= upper.
 
     A, L: LinearOperators with the same column count (L = Identity: plain l1; FirstDerivative2D: anisotropic TV, on fused kernels);
+    tv: 'aniso' (the l1 norm of L x) or 'iso' — lam sum over pixels of sqrt(h^2 + v^2), isotropic TV: the rows H[i][j] and V[i][j] of
+        the first differences of an image form one group, the last row's H, the last column's V and every further row (the temporal
+        rows of SpaceTimeDerivative: spatially isotropic, temporally l1) a group of their own.  The geometry is FirstDerivative2D's
+        (fused kernels) and SpaceTimeDerivative's own; tv_dims=(N, frames) gives it for any other operator whose rows are `frames`
+        blocks [H ; V] of N x N images and then a tail, such as SparseOp(first_derivative_2d(N, N)).  ValueError where it is missing
+        or disagrees with L.shape.  The objectives below then carry the group norms, and info['tv'] = 'iso';
     b: (m,) / (m,1); x0: (n,) / (n,1) or None (zeros), projected onto the box; lower / upper: scalars, -inf / +inf allowed.
     Steps: sigma and tau as given; if not both are, sigma tau normK2 = 0.95^2 and sigma / tau = ratio, with normK2 the caller's number
     or else operator_norm_sq([A, L], iters=30, seed=0) — an estimate from below, for which the 0.95 leaves room down to 0.9025 of the
@@ -189,6 +250,7 @@ def PDHG(A, b, L, lam, max_iter, tol=0, x0=None, x_true=None, lower=0.0, upper=n
         raise NotImplementedError("PDHG is not built for unknowns spread over ranks (eng.world > 1)")
     if L.shape[1] != A.shape[1]:
         raise ValueError(f"L has {L.shape[1]} columns, A has {A.shape[1]}")
+    _iso_geometry(L, tv, tv_dims)                # refused before the norm estimate is paid for
     lam = float(lam)
     if not (np.isfinite(lam) and lam >= 0):
         raise ValueError("PDHG: lam must be finite and >= 0")
@@ -205,7 +267,8 @@ def PDHG(A, b, L, lam, max_iter, tol=0, x0=None, x_true=None, lower=0.0, upper=n
         sigma, tau = pdhg_steps(normK2, ratio)
     delta = kwargs.get("delta", None)
     eta = float(kwargs.get("eta", 1.01))
-    run = PDHGRun(A, b, L, lam, sigma, tau, lower, upper, x0, max_iter, x_true, kwargs.get("history", True), kwargs.get("fused", None))
+    run = PDHGRun(A, b, L, lam, sigma, tau, lower, upper, x0, max_iter, x_true, kwargs.get("history", True), kwargs.get("fused", None),
+                  tv, tv_dims)
     if tol == 0 and delta is None:
         run.run(max_iter)                       # nothing is read back inside the loop -> one enqueue
     else:
@@ -227,6 +290,8 @@ def PDHG(A, b, L, lam, max_iter, tol=0, x0=None, x_true=None, lower=0.0, upper=n
                 "active": [int(c) for c in rows[:, 7]],
                 "sigma": float(sigma), "tau": float(tau), "normK2": None if normK2 is None else float(normK2),
                 "objectiveFinal": run.objective_at(x_fin)}
+    if run.geo is not None:
+        info["tv"] = run.tv
     if run.xt is not None:
         nxt = float(np.linalg.norm(_host(run.xt).astype(np.float64)))
         info["relError"] = list(np.sqrt(rows[:, 6]) / nxt)
