@@ -28,6 +28,51 @@ def test_library_builds_and_exports_every_declared_symbol():
     assert sorted(_lib.SIGNATURES) == syms
 
 
+def test_signatures_cover_the_header_with_known_kinds():
+    """The ctypes table is parsed from trk.h: it names what header_symbols() finds by another expression, in six kinds only."""
+    from trips_py_amd import _lib
+    kinds = {ctypes.c_int, ctypes.c_int64, ctypes.c_double, ctypes.c_float, ctypes.c_void_p, ctypes.c_char_p}
+    assert sorted(_lib.SIGNATURES) == header_symbols()
+    with open(os.path.join(REPO, "include", "trk.h")) as fh:
+        assert _lib.parse_signatures(fh.read()) == _lib.SIGNATURES
+    for name, (res, args) in _lib.SIGNATURES.items():
+        assert res in (ctypes.c_int, ctypes.c_char_p), name
+        assert isinstance(args, list) and set(args) <= kinds - {ctypes.c_char_p}, name
+
+
+def test_signatures_of_pinned_entries():
+    """Entries that together use every C kind of the header, written out as the hand-kept table had them (every pointer flavour —
+    POINTER(c_int), POINTER(c_double), POINTER(c_float), POINTER(c_void_p), handles, device pointers, streams — is a c_void_p)."""
+    from trips_py_amd import _lib
+    i, i64, d, p = ctypes.c_int, ctypes.c_int64, ctypes.c_double, ctypes.c_void_p
+    pinned = {
+        "trk_last_error": (ctypes.c_char_p, []),
+        "trk_op_apply": (i, [p, i, p, i64, p, i64, i, p, p]),
+        "trk_axpby": (i, [i64, d, p, p, i, p, d, p, p, i, p, p, p, p]),
+        "trk_csr_create": (i, [i64, i64, i64, p, p, p, p, p, p, p]),
+        "trk_timer_read": (i, [p, p, i, p]),
+        "trk_blockdiag_create": (i, [p, i, p]),
+        "trk_cgls_iterate_recompute": (i, [p, i, i, p, p, i64, i, p, p, p, p, i64, p, p, p, p, i, p, p, p, i, p]),
+        "trk_pdhg_iterate_iso": (i, [p, p, i, i, i, i, d, d, d, d, d, i, p, p, p, p, p, p, p, p, i64, i, p, p, p, p, i, p]),
+    }
+    for name, want in pinned.items():
+        assert _lib.SIGNATURES[name] == want, name
+
+
+def test_signature_parser_maps_every_kind_and_refuses_what_it_does_not_know():
+    from trips_py_amd import TrkError, _lib
+    i, p = ctypes.c_int, ctypes.c_void_p
+    got = _lib.parse_signatures("/* int trk_not(int a); */\nint trk_a(void); // int trk_nor(int a);\nconst char* trk_b();\n"
+                                "int trk_c(const float* x, trk_op* const* ops,\n          int64_t n, double c, float f, int k, trk_stream s);\n")
+    assert got == {"trk_a": (i, []), "trk_b": (ctypes.c_char_p, []),
+                   "trk_c": (i, [p, p, ctypes.c_int64, ctypes.c_double, ctypes.c_float, i, p])}
+    for bad in ("int trk_x(short n);", "int trk_x(unsigned int n);", "int trk_x(int64_t);", "int trk_x(double v[3]);",
+                "int trk_x(int n, ...);", "void trk_x(int n);", "trk_op trk_x(int n);", "int trk_x(int (*cb)(int), int n);",
+                "int\ntrk_x(int n);"):
+        with pytest.raises(TrkError, match="trk_x"):
+            _lib.parse_signatures(bad)
+
+
 def test_version_and_error_string_callable_without_gpu():
     from trips_py_amd import _lib
     lib = _lib.load()

@@ -22,10 +22,16 @@ def _blur(N=96):
     return A, xt, b
 
 
+def _ring_of_6(monkeypatch):
+    """Every History made from here on gets a ring of 6 slots: with 37 iterates the chunks wrap around it several times."""
+    from trips_py_amd import _io
+    orig = _io.History.__init__
+    monkeypatch.setattr(_io.History, "__init__", lambda self, eng, sp, count, nn, what, ring=None: orig(self, eng, sp, count, nn, what, ring=6))
+
+
 @pytest.mark.parametrize("spec", [4, "host", "file"])
 @pytest.mark.parametrize("fused", [False, True])
 def test_cgls_history_modes(spec, fused, tmp_path, monkeypatch):
-    from trips_py_amd import _io
     from trips_py_amd.solvers import CGLS
     A, xt, b = _blur()
     n = A.shape[1]
@@ -33,9 +39,7 @@ def test_cgls_history_modes(spec, fused, tmp_path, monkeypatch):
         spec = str(tmp_path / "cgls.npy")
     x0 = torch.zeros(n, device=b.device)
     xa, ia = CGLS(A, b, x0, 37, 0, xt, fused=fused)
-    # a ring of 6 slots for 37 iterates: the chunks wrap around it several times
-    orig = _io.History.__init__
-    monkeypatch.setattr(_io.History, "__init__", lambda self, eng, sp, count, nn, what, ring=None: orig(self, eng, sp, count, nn, what, ring=6))
+    _ring_of_6(monkeypatch)
     xb, ib = CGLS(A, b, x0, 37, 0, xt, fused=fused, history=spec)
     assert torch.equal(xa, xb) and np.array_equal(ia["relError"], ib["relError"])
     H = ib["xHistory"]
@@ -45,6 +49,66 @@ def test_cgls_history_modes(spec, fused, tmp_path, monkeypatch):
         got = H[j].reshape(-1)
         assert isinstance(got, torch.Tensor) and got.dtype == torch.float32      # torch callers read tensors, whatever the sink
         assert torch.equal(ref.float(), got.to(ref.device)), (j, k)
+
+
+def _np(v):
+    return (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)).reshape(-1)
+
+
+def _blur64(seed):
+    """A 64 x 64 Gaussian blur (four 32 x 32 tiles: neighbours on both axes) of the truth the MRNSD / PDHG problems are made of, 1 % noise."""
+    from mrnsd_cases import _truth
+    from trips_py_amd.operators import Blur2D
+    from trips_py_amd.problems import gauss_psf
+    A = Blur2D(gauss_psf((9, 9), (3, 3))[0], 64, 64)
+    xt = _truth(64, 64, seed).reshape(-1, 1)
+    bt = A @ xt
+    e = np.random.default_rng(seed + 1).standard_normal(bt.shape)
+    return A, xt, bt + 0.01 * np.linalg.norm(bt) / np.linalg.norm(e) * e
+
+
+def _cgls_form(**form):
+    from trips_py_amd.solvers import CGLS
+    from trips_py_amd.solvers.CGLS import CGLSRunFused
+    A, xt, b = _blur()
+    assert "tiled" not in form or CGLSRunFused.tiled_usable(A, A.engine)
+    x0 = torch.zeros(A.shape[1], device=b.device)
+    return lambda **kw: CGLS(A, b, x0, 37, 0, xt, **form, **kw)
+
+
+def _mrnsd():
+    from trips_py_amd.solvers import MRNSD
+    A, xt, b = _blur64(51)
+    return lambda **kw: MRNSD(A, b, None, 37, 0, xt, **kw)
+
+
+def _pdhg():
+    from trips_py_amd.operators import FirstDerivative2D, operator_norm_sq
+    from trips_py_amd.solvers import PDHG
+    A, xt, b = _blur64(53)
+    L = FirstDerivative2D(64)
+    normK2 = operator_norm_sq([A, L], iters=30, seed=0)
+    return lambda **kw: PDHG(A, b, L, 0.01, 37, 0, x_true=xt, normK2=normK2, fused=True, **kw)    # the fused TV kernels, or ValueError
+
+
+@pytest.mark.parametrize("spec", [4, "host"])
+@pytest.mark.parametrize("form", ["tiled1", "tiled2", "one_reduction", "mrnsd", "pdhg"])
+def test_c_loops_chunked_over_a_short_ring(form, spec, monkeypatch):
+    """The C loops the short ring of test_cgls_history_modes does not reach — the two tiled CGLS forms, the one-reduction form, MRNSD
+    and PDHG on its fused TV kernels — in chunks over a ring of 6 slots for 37 iterates: the same kernels in the same order as with the
+    on-device history, so every kept iterate, the returned x and the reported norms are equal bit for bit."""
+    solve = {"tiled1": lambda: _cgls_form(tiled=1), "tiled2": lambda: _cgls_form(tiled=2),
+             "one_reduction": lambda: _cgls_form(one_reduction=True), "mrnsd": _mrnsd, "pdhg": _pdhg}[form]()
+    xa, ia = solve()
+    _ring_of_6(monkeypatch)
+    xb, ib = solve(history=spec)
+    assert ia["its"] == ib["its"] == 37
+    assert np.array_equal(_np(xa), _np(xb))
+    assert np.array_equal(ia["relResidual"], ib["relResidual"]) and np.array_equal(ia["relError"], ib["relError"])
+    H = ib["xHistory"]
+    assert H.iterations == (list(range(37)) if spec == "host" else [3, 7, 11, 15, 19, 23, 27, 31, 35, 36])
+    for j, k in enumerate(H.iterations):
+        assert np.array_equal(_np(H[j]), _np(ia["xHistory"][k])), (j, k)
 
 
 @pytest.mark.parametrize("spec", [2, "host"])

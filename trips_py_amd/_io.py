@@ -23,6 +23,11 @@ def as_operator(A, role="A"):
                     f"FirstDerivative2D, ...); got {type(A).__name__}.  The engine has no host/NumPy operator path.")
 
 
+def _host(v):
+    """A device / host tensor or anything array-like as a NumPy array on the host."""
+    return v.detach().to("cpu").numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+
+
 class Formatter:
     """Remembers whether the caller speaks NumPy or torch and formats vectors accordingly."""
 

@@ -7,6 +7,7 @@ travels with the source snapshot.
 """
 import ctypes
 import os
+import re
 import shutil
 import subprocess
 import sys
@@ -123,245 +124,43 @@ def _build_locked(force, verbose):
 
 
 # ----------------------------------------------------------------------------- ctypes signatures
-c_f32p = ctypes.c_void_p     # device pointers travel as integers (tensor.data_ptr())
-c_f64p = ctypes.c_void_p
-c_i64 = ctypes.c_int64
-c_int = ctypes.c_int
-c_dbl = ctypes.c_double
-c_op = ctypes.c_void_p
-c_stream = ctypes.c_void_p
+# include/trk.h is the only place the ABI is written down: a width, a count or an order that differed between a hand-kept table and
+# the header would load cleanly and hand a kernel a garbage length or address.
+_BY_VALUE = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "double": ctypes.c_double, "float": ctypes.c_float,
+             "trk_stream": ctypes.c_void_p}           # typedef void* trk_stream (hipStream_t)
+_DECL = re.compile(r"^[ \t]*(\w[\w \t*]*?)\b(trk_\w+)\s*\(([^()]*)\)\s*;", re.M)
 
-SIGNATURES = {
-    "trk_version": (c_int, []),
-    "trk_last_error": (ctypes.c_char_p, []),
-    "trk_device_info": (c_int, [ctypes.POINTER(c_int), ctypes.POINTER(c_int), ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
-    "trk_blur2d_create": (c_int, [ctypes.POINTER(c_dbl), c_int, c_int, c_int, c_int, ctypes.POINTER(c_op)]),
-    "trk_blur2d_create_bc": (c_int, [ctypes.POINTER(c_dbl), c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_op)]),
-    "trk_blur2d_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)]),
-    "trk_blur2d_path": (c_int, [c_op, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
-    "trk_blur2d_set_path": (c_int, [c_op, c_int]),
-    "trk_radon2d_create": (c_int, [c_int, c_int, ctypes.POINTER(c_dbl), c_int, c_dbl, ctypes.POINTER(c_op)]),
-    "trk_radon2d_dynamic_create": (c_int, [c_int, c_int, ctypes.POINTER(c_dbl), c_int, c_int, c_dbl, ctypes.POINTER(c_op)]),
-    "trk_fanbeam2d_create": (c_int, [c_int, c_int, c_dbl, c_dbl, c_dbl, ctypes.POINTER(c_dbl), c_int, ctypes.POINTER(c_op)]),
-    "trk_deriv2d_create": (c_int, [c_int, ctypes.POINTER(c_op)]),
-    "trk_spacetime_create": (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(c_op)]),
-    "trk_spacetime_set_halo": (c_int, [c_op, c_f32p, c_f32p]),
-    "trk_csr_create": (c_int, [c_i64, c_i64, c_i64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                               ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(c_op)]),
-    "trk_framelet2d_create": (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(c_dbl), c_int, c_int, ctypes.POINTER(c_dbl),
-                                      ctypes.POINTER(c_op)]),
-    "trk_blockdiag_create": (c_int, [ctypes.POINTER(c_op), c_int, ctypes.POINTER(c_op)]),
-    "trk_op_shape": (c_int, [c_op, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
-    "trk_op_apply": (c_int, [c_op, c_int, c_f32p, c_i64, c_f32p, c_i64, c_int, c_f64p, c_stream]),
-    "trk_op_destroy": (c_int, [c_op]),
-    "trk_timer_create": (c_int, [c_int, ctypes.POINTER(ctypes.c_void_p)]),
-    "trk_timer_reset": (c_int, [ctypes.c_void_p]),
-    "trk_timer_read": (c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_float), c_int, ctypes.POINTER(c_int)]),
-    "trk_timer_destroy": (c_int, [ctypes.c_void_p]),
-    "trk_op_set_timer": (c_int, [c_op, ctypes.c_void_p, c_int]),
-    "trk_dot": (c_int, [c_f32p, c_f32p, c_i64, c_f64p, c_stream]),
-    "trk_nrm2sq": (c_int, [c_f32p, c_i64, c_f64p, c_stream]),
-    "trk_diff_nrm2sq": (c_int, [c_f32p, c_f32p, c_i64, c_f64p, c_stream]),
-    "trk_axpby": (c_int, [c_i64, c_dbl, c_f64p, c_f64p, c_int, c_f32p, c_dbl, c_f64p, c_f64p, c_int, c_f32p, c_f32p, c_f64p, c_stream]),
-    "trk_scale_dot": (c_int, [c_i64, c_dbl, c_f64p, c_f64p, c_int, c_f32p, c_f32p, c_f32p, c_f64p, c_stream]),
-    "trk_mul": (c_int, [c_i64, c_f32p, c_f32p, c_f32p, c_stream]),
-    "trk_mul_diff": (c_int, [c_i64, c_f32p, c_f32p, c_f32p, c_f32p, c_stream]),
-    "trk_group_weights": (c_int, [c_f32p, c_i64, c_int, c_dbl, c_dbl, c_int, c_f32p, c_stream]),
-    "trk_isotv_weights": (c_int, [c_f32p, c_int, c_int, c_f32p, c_i64, c_dbl, c_dbl, c_f32p, c_stream]),
-    "trk_tv_weights": (c_int, [c_op, c_f32p, c_dbl, c_dbl, c_f32p, c_stream]),
-    "trk_arnoldi_step": (c_int, [c_op, c_f32p, c_i64, c_int, c_f32p, c_f64p, c_int, c_f64p, c_f64p, c_stream]),
-    "trk_host_gram_gcv": (c_int, [ctypes.POINTER(ctypes.c_void_p), ctypes.c_void_p, ctypes.c_void_p, c_int, ctypes.c_void_p, ctypes.c_void_p,
-                                 c_int, c_dbl, ctypes.POINTER(c_dbl), ctypes.c_void_p, ctypes.POINTER(c_int)]),
-    "trk_hlsqr_select": (c_int, [ctypes.c_void_p, c_int, ctypes.c_void_p, ctypes.c_void_p, c_int, c_dbl, c_dbl, ctypes.c_void_p, c_dbl, c_int,
-                                c_f32p, c_i64, c_i64, c_f32p, c_f32p, c_f64p, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_dbl),
-                                ctypes.POINTER(c_int), c_stream]),
-    "trk_hgmres_create": (c_int, [c_op, c_f32p, c_i64, c_int, c_f32p, c_f64p, c_int, c_f64p, c_f64p, ctypes.c_void_p,
-                                 ctypes.POINTER(ctypes.c_void_p), c_int, c_dbl, c_stream,
-                                 ctypes.POINTER(ctypes.c_void_p)]),
-    "trk_hgmres_destroy": (c_int, [ctypes.c_void_p]),
-    "trk_hgmres_start": (c_int, [ctypes.c_void_p]),
-    "trk_hgmres_dp": (c_int, [ctypes.c_void_p, c_f32p, c_dbl, c_dbl, c_dbl, ctypes.POINTER(ctypes.POINTER(c_dbl))]),
-    "trk_hgmres_fixed_lambda": (c_int, [ctypes.c_void_p, c_dbl]),
-    "trk_hgmres_stats": (c_int, [ctypes.c_void_p, ctypes.POINTER(c_dbl)]),
-    "trk_hgmres_iter": (c_int, [ctypes.c_void_p, c_int, c_int, c_int, c_f32p, c_f32p, c_f64p, c_int, ctypes.POINTER(c_int),
-                               ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl), ctypes.POINTER(c_int)]),
-    "trk_hgmres_hessenberg": (c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.POINTER(c_dbl)), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
-    "trk_arnoldi_step_post_dot": (c_int, [c_op, c_f32p, c_i64, c_int, c_f32p, c_f64p, c_int, c_f64p, c_f64p, ctypes.c_void_p, c_int, c_int, c_int,
-                                         c_int, c_f32p, c_int, c_stream]),
-    "trk_arnoldi_step_post_at": (c_int, [c_op, c_f32p, c_i64, c_int, c_f32p, c_f64p, c_int, c_f64p, c_f64p, ctypes.c_void_p, c_int, c_int, c_int,
-                                        c_int, c_stream]),
-    "trk_mailbox_doubles": (c_int, [ctypes.c_void_p]),
-    "trk_mailbox_slots": (c_int, [ctypes.c_void_p]),
-    "trk_host_worker_post_hess_fixed": (c_int, [ctypes.c_void_p, ctypes.c_void_p, c_i64, c_i64, c_int, c_dbl, c_dbl]),
-    "trk_arnoldi_step_post": (c_int, [c_op, c_f32p, c_i64, c_int, c_f32p, c_f64p, c_int, c_f64p, c_f64p, ctypes.c_void_p, c_int, c_int, c_int,
-                                     c_stream]),
-    "trk_tv_grad": (c_int, [c_op, c_f32p, c_f32p, c_f32p, c_dbl, c_f32p, c_stream]),
-    "trk_tv_halo": (c_int, [c_op, c_f32p, c_f32p]),
-    "trk_tv_grad_dot": (c_int, [c_op, c_f32p, c_f32p, c_f32p, c_dbl, c_f32p, c_f32p, c_f64p, c_stream]),
-    "trk_tv_grad_dot_xsq": (c_int, [c_op, c_f32p, c_f32p, c_f32p, c_dbl, c_f32p, c_f32p, c_f64p, c_f64p, c_stream]),
-    "trk_mm_weights": (c_int, [c_i64, c_f32p, c_f32p, c_dbl, c_dbl, c_f32p, c_stream]),
-    "trk_cgls_update_xr": (c_int, [c_i64, c_i64, c_f64p, c_f64p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f64p, c_stream]),
-    "trk_op_fused_caps": (c_int, [c_op, ctypes.POINTER(c_int)]),
-    "trk_op_axpby_caps": (c_int, [c_op, ctypes.POINTER(c_int)]),
-    "trk_op_flush": (c_int, [c_op, c_stream]),
-    "trk_op_apply_axpby": (c_int, [c_op, c_int, c_f32p, c_dbl, c_f64p, c_f64p, c_int, c_dbl, c_f64p, c_f64p, c_int, c_f32p,
-                                   c_f32p, c_f64p, c_int, c_stream]),
-    "trk_op_apply_fused": (c_int, [c_op, c_int, c_f32p, c_f32p, c_dbl, c_f64p, c_int, c_f64p, c_int, c_f32p, c_f32p, c_f64p, c_int, ctypes.POINTER(c_int), c_stream]),
-    "trk_cgls_x_update": (c_int, [c_i64, c_f64p, c_int, c_f64p, c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_f64p, c_f64p, c_f64p, c_int, ctypes.POINTER(c_int), c_stream]),
-    "trk_finalize_batched": (c_int, [c_f64p, c_int, c_int, c_int, c_f64p, c_int, c_stream]),
-    "trk_cgls_update_xr_deferred": (c_int, [c_i64, c_i64, c_f64p, c_f64p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f64p, c_int, ctypes.POINTER(c_int), c_stream]),
-    "trk_bidiag_tikhonov": (c_int, [c_f64p, c_i64, c_f64p, c_i64, c_int, c_dbl, c_f64p, c_f64p, c_int, c_f64p, c_int,
-                                   c_stream]),
-    "trk_host_dp_newton": (c_int, [c_f64p, c_f64p, c_int, c_dbl, c_dbl, ctypes.POINTER(c_dbl), ctypes.POINTER(c_int),
-                                  ctypes.POINTER(c_int)]),
-    "trk_host_gcv_fminbound": (c_int, [c_f64p, c_f64p, c_int, c_dbl, c_dbl, c_dbl, c_dbl, c_int, ctypes.POINTER(c_dbl), ctypes.POINTER(c_dbl), ctypes.POINTER(c_int)]),
-    "trk_host_dp_bidiag": (c_int, [c_f64p, c_f64p, c_int, c_f64p, c_dbl, c_dbl, ctypes.POINTER(c_dbl), ctypes.POINTER(c_int),
-                                   ctypes.POINTER(c_int), ctypes.POINTER(c_dbl)]),
-    "trk_host_gcv_bidiag": (c_int, [c_f64p, c_f64p, c_int, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl, c_int, ctypes.POINTER(c_dbl),
-                                    ctypes.POINTER(c_dbl), ctypes.POINTER(c_int)]),
-    "trk_cgls_iterate": (c_int, [c_op, c_int, c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_i64, c_int, c_f32p, c_f32p,
-                                 c_f64p, c_f64p, c_int, ctypes.POINTER(c_int), c_f64p, c_f64p, c_int, c_int, c_stream]),
-    "trk_cgls_update_xr_src": (c_int, [c_i64, c_i64, c_f64p, c_int, c_f64p, c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
-                                       c_f32p, c_f64p, c_f64p, c_int, ctypes.POINTER(c_int), c_stream]),
-    "trk_cgls_update_grouping": (c_int, [c_i64]),
-    "trk_cgls_r_update": (c_int, [c_i64, c_f64p, c_f64p, c_int, c_f32p, c_f32p, c_f64p, c_stream]),
-    "trk_cgls_xp_update": (c_int, [c_i64, c_f64p, c_f64p, c_f64p, c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f64p, c_f64p,
-                                   c_int, ctypes.POINTER(c_int), c_stream]),
-    "trk_cgls_p_update": (c_int, [c_i64, c_f32p, c_f32p, c_f64p, c_int, c_f64p, c_f64p, c_stream]),
-    "trk_cgls_p_update_to": (c_int, [c_i64, c_f32p, c_f32p, c_f32p, c_f64p, c_int, c_f64p, c_f64p, c_stream]),
-    "trk_cgls_xs_update": (c_int, [c_i64, c_int, c_int, c_f64p, c_f64p, c_int, c_f32p, c_f32p, c_f32p, c_i64, c_int, c_int, c_f32p,
-                                   c_f32p, c_f32p, c_f32p, c_f64p, c_int, ctypes.POINTER(c_int), c_stream]),
-    "trk_cgls_x_batch": (c_int, [c_i64]),
-    "trk_cgls_iterate_xbatch": (c_int, [c_op, c_int, c_int, c_f32p, c_f32p, c_i64, c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_i64,
-                                        c_f32p, c_f32p, c_f64p, c_f64p, c_int, ctypes.POINTER(c_int), c_f64p, c_f64p, c_int,
-                                        c_stream]),
-    "trk_op_recompute_caps": (c_int, [c_op, ctypes.POINTER(c_int)]),
-    "trk_op_apply_sumsq_raw": (c_int, [c_op, c_int, c_f32p, c_f64p, c_int, ctypes.POINTER(c_int), c_stream]),
-    "trk_op_apply_ratio": (c_int, [c_op, c_int, c_f32p, c_int, c_dbl, c_f64p, c_int, c_f64p, c_int, c_f32p, c_f32p, c_f64p, c_int,
-                                   c_stream]),
-    "trk_cgls_xs_update_x": (c_int, [c_i64, c_int, c_int, c_f64p, c_f32p, c_f32p, c_f32p, c_i64, c_int, c_int, c_f32p, c_f32p,
-                                     c_f64p, c_int, ctypes.POINTER(c_int), c_stream]),
-    "trk_cgls_recompute": (c_int, [c_i64]),
-    "trk_cgls_iterate_recompute": (c_int, [c_op, c_int, c_int, c_f32p, c_f32p, c_i64, c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_i64,
-                                           c_f32p, c_f32p, c_f64p, c_f64p, c_int, ctypes.POINTER(c_int), c_f64p, c_f64p, c_int,
-                                           c_stream]),
-    "trk_cgls_iterate_fused": (c_int, [c_op, c_int, c_int, c_f32p, c_i64, c_f32p, c_i64, c_f32p, c_f32p, c_f32p, c_i64, c_int,
-                                       c_f32p, c_f32p, c_f64p, c_f64p, c_f64p, c_int, c_f64p, c_int, ctypes.POINTER(c_int),
-                                       ctypes.POINTER(c_int), c_stream]),
-    "trk_cgls_tiled_caps": (c_int, [c_op, c_int, c_int, ctypes.POINTER(c_int)]),
-    "trk_cgls_iterate_tiled": (c_int, [c_op, c_int, c_int, c_f32p, c_i64, c_f32p, c_i64, c_f32p, c_f32p, c_i64, c_int,
-                                       c_f32p, c_f32p, c_f64p, c_f64p, c_f64p, c_int, c_f64p, c_int, ctypes.POINTER(c_int),
-                                       ctypes.POINTER(c_int), c_stream]),
-    "trk_cgls_iterate_tiled2": (c_int, [c_op, c_int, c_int, c_f32p, c_f32p, c_f32p, c_i64, c_f32p, c_f32p, c_i64, c_int,
-                                        c_f32p, c_f32p, c_f64p, c_f64p, c_f64p, c_int, c_f64p, c_int, ctypes.POINTER(c_int),
-                                        ctypes.POINTER(c_int), c_stream]),
-    "trk_mrnsd_init": (c_int, [c_i64, c_i64, c_f32p, c_f32p, c_f32p, c_f32p, c_f64p, c_int, c_f64p, ctypes.POINTER(c_int), c_stream]),
-    "trk_mrnsd_update": (c_int, [c_i64, c_i64, c_f64p, c_int, c_f64p, c_int, c_f64p, c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
-                                 c_f32p, c_f32p, c_f64p, c_int, c_f64p, c_f64p, c_f64p, c_int, ctypes.POINTER(c_int), c_stream]),
-    "trk_mrnsd_finish": (c_int, [c_f64p, c_int, c_f64p, c_int, c_f64p, c_stream]),
-    "trk_mrnsd_iterate": (c_int, [c_op, c_int, c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_i64, c_int, c_f32p, c_f32p,
-                                  c_f64p, c_f64p, c_int, c_f64p, c_int, ctypes.POINTER(c_int), c_f64p, c_int, c_stream]),
-    "trk_pdhg_blocks": (c_int, [c_i64, c_i64, c_i64, c_op, ctypes.POINTER(c_int)]),
-    "trk_pdhg_dual_p": (c_int, [c_i64, c_dbl, c_f32p, c_f32p, c_f32p, c_f64p, c_int, ctypes.POINTER(c_int), c_stream]),
-    "trk_pdhg_dual_q": (c_int, [c_i64, c_dbl, c_dbl, c_f32p, c_f32p, c_f64p, c_int, ctypes.POINTER(c_int), c_stream]),
-    "trk_pdhg_primal": (c_int, [c_i64, c_dbl, c_dbl, c_dbl, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f64p, c_int,
-                                ctypes.POINTER(c_int), c_stream]),
-    "trk_pdhg_fused_caps": (c_int, [c_op, ctypes.POINTER(c_int)]),
-    "trk_pdhg_tv_dual": (c_int, [c_op, c_dbl, c_dbl, c_f32p, c_f32p, c_f64p, c_int, ctypes.POINTER(c_int), c_stream]),
-    "trk_pdhg_tv_primal": (c_int, [c_op, c_dbl, c_dbl, c_dbl, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f64p, c_int,
-                                   ctypes.POINTER(c_int), c_stream]),
-    "trk_pdhg_iterate": (c_int, [c_op, c_op, c_int, c_int, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl, c_int, c_f32p, c_f32p, c_f32p, c_f32p,
-                                 c_f32p, c_f32p, c_f32p, c_f32p, c_i64, c_int, c_f32p, c_f32p, c_f32p, c_f64p, c_int, c_stream]),
-    "trk_pdhg_blocks_iso": (c_int, [c_i64, c_i64, c_i64, c_int, c_int, c_op, ctypes.POINTER(c_int)]),
-    "trk_pdhg_dual_q_iso": (c_int, [c_int, c_int, c_i64, c_dbl, c_dbl, c_f32p, c_f32p, c_f64p, c_int, ctypes.POINTER(c_int), c_stream]),
-    "trk_pdhg_tv_dual_iso": (c_int, [c_op, c_dbl, c_dbl, c_f32p, c_f32p, c_f64p, c_int, ctypes.POINTER(c_int), c_stream]),
-    "trk_pdhg_iterate_iso": (c_int, [c_op, c_op, c_int, c_int, c_int, c_int, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl, c_int, c_f32p, c_f32p,
-                                     c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_i64, c_int, c_f32p, c_f32p, c_f32p, c_f64p, c_int,
-                                     c_stream]),
-    "trk_gemv_t": (c_int, [c_f32p, c_i64, c_int, c_i64, c_f32p, c_f32p, c_f64p, c_stream]),
-    "trk_gemv_t_x": (c_int, [c_f32p, c_i64, c_int, c_i64, c_f32p, c_f32p, c_f64p, c_f64p, c_stream]),
-    "trk_gemv_t2": (c_int, [c_f32p, c_i64, c_int, c_i64, c_f32p, c_f32p, c_f64p, c_stream]),
-    "trk_gemv_tn": (c_int, [c_f32p, c_i64, c_int, c_i64, ctypes.POINTER(ctypes.c_void_p), c_int, c_f64p, c_stream]),
-    "trk_gram_row_from_sweep": (c_int, [c_f64p, c_int, c_int, c_f64p, c_f64p, c_f64p, c_f64p, c_f64p, c_f64p, c_stream]),
-    "trk_gram_tikhonov": (c_int, [c_f64p, c_int, c_f64p, c_int, c_f64p, c_int, c_dbl, c_f64p, c_int, c_int, c_f64p, c_stream]),
-    "trk_hess_tikhonov": (c_int, [c_f64p, c_int, c_f64p, c_f64p, c_int, c_f64p, c_f64p, c_f64p, c_dbl, c_int, c_dbl, c_int, c_f64p,
-                                  c_stream]),
-    "trk_cgs_coeffs": (c_int, [c_f64p, c_int, c_f64p, c_f64p, c_int, c_int, c_f64p, c_stream]),
-    "trk_gks_rows_solve": (c_int, [c_f64p, c_f64p, c_int, c_int, c_f64p, c_f64p, c_f64p, c_f64p, c_f64p, c_f64p, c_f64p, c_f64p, c_f64p, c_dbl,
-                                   c_f64p, c_int, c_int, c_f64p, c_stream]),
-    "trk_cgs_coeffs_rho": (c_int, [c_f64p, c_int, c_f64p, c_f64p, c_int, c_int, c_f64p, c_f64p, c_f64p, c_stream]),
-    "trk_gemv_orth_iterate": (c_int, [c_f32p, c_i64, c_int, c_i64, c_f32p, c_f64p, c_f64p, c_f64p, c_f32p, c_f32p, c_f32p, c_f64p, c_int,
-                                      ctypes.POINTER(c_int), c_f64p, c_stream]),
-    "trk_gemv_nt": (c_int, [c_f32p, c_i64, c_int, c_i64, c_f64p, c_f32p, c_f32p, c_f64p, c_stream]),
-    "trk_gemv_n_err": (c_int, [c_f32p, c_i64, c_int, c_i64, c_f64p, c_f32p, c_f32p, c_f64p, c_int, ctypes.POINTER(c_int), c_stream]),
-    "trk_host_worker_create": (c_int, [ctypes.POINTER(ctypes.c_void_p)]),
-    "trk_host_worker_destroy": (c_int, [ctypes.c_void_p]),
-    "trk_host_worker_post_gcv_bidiag": (c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_int, c_dbl, c_dbl, c_dbl, c_dbl,
-                                                c_dbl, c_int]),
-    "trk_host_worker_post_dp_bidiag": (c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_int, ctypes.c_void_p, c_dbl, c_dbl]),
-    "trk_host_worker_collect": (c_int, [ctypes.c_void_p, ctypes.POINTER(c_dbl), ctypes.POINTER(c_int)]),
-    "trk_host_worker_set_lapack": (c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
-    "trk_host_worker_post_hess_gcv": (c_int, [ctypes.c_void_p, ctypes.c_void_p, c_i64, c_i64, c_int, c_dbl, c_dbl, c_dbl, c_dbl, c_dbl, c_int]),
-    "trk_host_worker_post_hess_dp": (c_int, [ctypes.c_void_p, ctypes.c_void_p, c_i64, c_i64, c_int, c_dbl, ctypes.c_void_p, c_dbl, c_dbl]),
-    "trk_host_worker_collect_vec": (c_int, [ctypes.c_void_p, ctypes.POINTER(c_dbl), ctypes.POINTER(c_int), ctypes.c_void_p, c_int,
-                                            ctypes.POINTER(c_dbl)]),
-    "trk_scalars_put": (c_int, [c_f64p, ctypes.c_void_p, c_int, c_stream]),
-    "trk_mailbox_create": (c_int, [c_int, c_int, ctypes.POINTER(ctypes.c_void_p)]),
-    "trk_mailbox_destroy": (c_int, [ctypes.c_void_p]),
-    "trk_mailbox_host": (c_int, [ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p)]),
-    "trk_mailbox_post": (c_int, [ctypes.c_void_p, c_int, c_f64p, c_int, c_int, c_stream]),
-    "trk_mailbox_wait": (c_int, [ctypes.c_void_p, c_int]),
-    "trk_mailbox_post_sum": (c_int, [ctypes.c_void_p, c_int, c_f64p, c_int, c_int, c_f64p, c_int, c_f64p, c_int, c_stream]),
-    "trk_gk_step_post": (c_int, [c_op, c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_f64p, c_int, c_int, c_int, c_f32p, c_f64p, c_int,
-                                 ctypes.POINTER(c_int), ctypes.c_void_p, c_int, c_f64p, c_int, c_int, c_f64p, c_int, c_f64p, c_int,
-                                 c_stream]),
-    "trk_gk_step_lsqr": (c_int, [c_op, c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_f64p, c_int, c_int, c_int, c_f32p, c_f32p, c_f32p, c_f32p,
-                                 c_f64p, c_int, ctypes.POINTER(c_int), c_dbl, c_f64p, c_f64p, c_stream]),
-    "trk_gk_step_proj": (c_int, [c_op, c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_f64p, c_int, c_int, c_int, c_f32p, c_f64p, c_int,
-                                 ctypes.POINTER(c_int), c_stream]),
-    "trk_host_bidiag_tikhonov": (c_int, [ctypes.c_void_p, ctypes.c_void_p, c_int, c_dbl, c_dbl, c_int, ctypes.c_void_p]),
-    "trk_gemv_n_hosty": (c_int, [c_f32p, c_i64, c_int, c_i64, ctypes.c_void_p, c_f32p, c_f32p, c_f64p, c_int, ctypes.POINTER(c_int),
-                                 c_stream]),
-    "trk_gk_step": (c_int, [c_op, c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_f64p, c_int, c_int, c_int, c_stream]),
-    "trk_wgram_tv_precision": (c_int, [c_int]),
-    "trk_wgram_tv_last_probe": (c_int, [ctypes.POINTER(c_dbl)]),
-    "trk_radon2d_apply_ref": (c_int, [c_op, c_int, c_int, c_int, ctypes.c_void_p, ctypes.c_void_p, c_stream]),
-    "trk_radon2d_set_arithmetic": (c_int, [c_op, c_int]),
-    "trk_radon2d_set_ref_sums": (c_int, [c_op, c_int, c_int]),
-    "trk_ref_axpby": (c_int, [c_int, c_i64, c_dbl, c_f64p, c_f64p, c_int, ctypes.c_void_p, c_dbl, c_f64p, c_f64p, c_int, ctypes.c_void_p,
-                              ctypes.c_void_p, c_f64p, c_stream]),
-    "trk_gk_lsqr_chain": (c_int, [c_op, c_int, c_int, ctypes.c_void_p, c_int, c_dbl, ctypes.c_void_p, ctypes.c_void_p, c_f64p, c_f64p,
-                                  c_stream]),
-    "trk_lsqr_damped_update": (c_int, [c_f32p, c_f32p, c_f32p, c_f32p, c_i64, c_f32p, c_f64p, c_int, ctypes.POINTER(c_int),
-                                       c_f64p, c_f64p, c_f64p, c_dbl, c_f64p, c_f64p, c_int, c_stream]),
-    "trk_gemv_n": (c_int, [c_f32p, c_i64, c_int, c_i64, c_f64p, c_dbl, c_f32p, c_dbl, c_f32p, c_f64p, c_stream]),
-    "trk_comm_unique_id": (c_int, [ctypes.c_void_p]),
-    "trk_comm_init": (c_int, [ctypes.c_void_p, c_int, c_int, ctypes.POINTER(ctypes.c_void_p)]),
-    "trk_comm_attach": (c_int, [ctypes.c_void_p, c_int, c_int, ctypes.POINTER(ctypes.c_void_p)]),
-    "trk_comm_info": (c_int, [ctypes.c_void_p, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
-    "trk_comm_destroy": (c_int, [ctypes.c_void_p]),
-    "trk_allreduce_f64": (c_int, [ctypes.c_void_p, c_f64p, c_int, c_stream]),
-    "trk_halo_exchange": (c_int, [ctypes.c_void_p, c_f32p, c_int, c_f32p, c_int, c_i64, c_stream]),
-    "trk_halo_exchange2": (c_int, [ctypes.c_void_p, c_f32p, c_f32p, c_f32p, c_f32p, c_i64, c_stream]),
-    "trk_dot_pair": (c_int, [c_f32p, c_f32p, c_i64, c_f64p, c_stream]),
-    "trk_cgls_sharded_update": (c_int, [c_i64, c_i64, c_f64p, c_f64p, c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
-                                        c_f32p, c_f32p, c_f64p, c_f64p, c_f64p, c_int, ctypes.POINTER(c_int), c_stream]),
-    "trk_cgls_sharded_scalars": (c_int, [c_f32p, c_f32p, c_i64, c_f64p, c_int, c_f64p, c_stream]),
-    "trk_cgls_iterate_sharded": (c_int, [c_op, ctypes.c_void_p, c_int, c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_i64,
-                                         c_int, c_f32p, c_f32p, c_f64p, c_f64p, c_f64p, c_int, ctypes.POINTER(c_int), c_f64p, c_int,
-                                         ctypes.POINTER(c_int), c_stream]),
-    "trk_wgram_tv_z": (c_int, [c_f32p, c_i64, c_int, c_int, c_f32p, c_f64p, c_f32p, c_f64p, c_stream]),
-    "trk_wgram_tv": (c_int, [c_f32p, c_i64, c_int, c_int, c_f32p, c_f64p, c_stream]),
-    "trk_wgram": (c_int, [c_f32p, c_i64, c_int, c_i64, c_f32p, c_f32p, c_f64p, c_f64p, c_f64p, c_stream]),
-    "trk_dense_svd_f64_dims": (c_int, [c_i64, c_i64, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
-    "trk_dense_svd_f64": (c_int, [c_f64p, c_i64, c_i64, c_i64, c_f64p, c_i64, c_f64p, c_i64, c_f64p, c_f64p, c_i64, c_dbl, c_int,
-                                  ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_stream]),
-    "trk_dense_svd_carry_f64_dims": (c_int, [c_i64, c_i64, c_i64, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
-    "trk_dense_svd_carry_f64": (c_int, [c_f64p, c_i64, c_i64, c_i64, c_f64p, c_i64, c_f64p, c_i64, c_i64, c_f64p, c_f64p, c_i64, c_dbl,
-                                        c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int), c_stream]),
-    "trk_dense_colnorm_f64": (c_int, [c_f64p, c_i64, c_i64, c_i64, c_f64p, c_stream]),
-    "trk_dense_gemv_f64": (c_int, [c_int, c_i64, c_i64, c_f64p, c_i64, c_f64p, c_f64p, c_dbl, c_dbl, c_f64p, c_stream]),
-}
+
+def parse_signatures(header):
+    """name -> (restype, [argtypes]) for every `ret trk_name(args);` in the text of trk.h.  Every pointer — device and host arrays,
+    handles, out-parameters — is a c_void_p: device pointers travel as integers (tensor.data_ptr()), and c_void_p also takes
+    byref(...), ctypes arrays and pointers, and None.  A type that is not spelled out here raises; nothing is guessed."""
+    table = {}
+    header = re.sub(r"/\*.*?\*/|//[^\n]*", " ", header, flags=re.S)
+    for ret, name, args in _DECL.findall(header):
+        def kind(words):
+            if "*" in words:
+                return ctypes.c_void_p
+            if len(words) != 1 or words[0] not in _BY_VALUE:
+                raise TrkError(f"trk.h: no ctypes mapping for '{' '.join(words)}' in: {' '.join((ret + name).split())}(...)")
+            return _BY_VALUE[words[0]]
+
+        rtype, *atypes = [[w for w in part.replace("*", " * ").split() if w != "const"] for part in [ret] + args.split(",")]
+        if atypes in ([[]], [["void"]]):
+            atypes = []
+        if not all(w == "*" or w.isidentifier() for words in atypes for w in words):       # arrays, bit widths, defaults
+            raise TrkError(f"trk.h: cannot read the arguments of {name}: ({' '.join(args.split())})")
+        # an argument is its type, then its name (a pointer may go without): a by-value argument without a name keeps no type and is refused
+        atypes = [w if w[-1:] == ["*"] else w[:-1] for w in atypes]
+        table[name] = (ctypes.c_char_p if rtype == ["char", "*"] else kind(rtype), [kind(w) for w in atypes])
+    skipped = set(re.findall(r"\b(trk_\w+)\s*\(", header)) - set(table)     # a declaration _DECL cannot read must not go unbound
+    if skipped:
+        raise TrkError(f"trk.h: cannot read the declaration of {sorted(skipped)}")
+    return table
+
+
+with open(os.path.join(INCLUDE, "trk.h")) as _fh:
+    SIGNATURES = parse_signatures(_fh.read())
 
 _lib = None
 

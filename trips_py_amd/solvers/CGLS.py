@@ -10,35 +10,12 @@ keeping the history costs no extra traffic.  Sharded problems all-reduce 1 + 4 d
 """
 import numpy as np
 
-from .._io import Formatter, History, as_operator
+from .._io import Formatter, as_operator
 from ..engine import Coef
+from ._run import IterationRun, _ShiftedRows
 
 
-class _ShiftedRows:
-    """A [rows, n] device block seen `shift` rows further on: what the C iteration loops take when iterate j is to land in
-    ring slot (j + shift) instead of row j (they only ask for the base address and the row stride)."""
-
-    def __init__(self, t, shift):
-        self.t, self.shift = t, int(shift)
-
-    def data_ptr(self):
-        return self.t.data_ptr() + self.shift * self.t.stride(0) * self.t.element_size()
-
-    def stride(self, dim):
-        return self.t.stride(dim)
-
-    def row(self, j):
-        return self.t[j + self.shift]
-
-
-def _row_of(X, j, keep):
-    """Row of the block the C loop wrote iterate j (0-based) to."""
-    if isinstance(X, _ShiftedRows):
-        return X.row(j)
-    return X[j] if keep else X[j & 1]
-
-
-class CGLSRun:
+class CGLSRun(IterationRun):
     """The CGLS recurrence as an object: `step()` enqueues one iteration (no host sync), `rows()` downloads the
     per-iteration scalars.  `CGLS()` below and bench.py both drive this one implementation.
 
@@ -57,16 +34,10 @@ class CGLSRun:
 
     def __init__(self, A, b, x0, max_iter, x_true=None, history=True, defer_norms=False, grouping=None, x_batch=None,
                  recompute=None):
-        self.A = A = as_operator(A)
-        self.eng = eng = A.engine
+        super().__init__(A, b, max_iter, x_true, history, "CGLS xHistory")
+        A, eng, max_iter = self.A, self.eng, self.max_iter
         m, n = A.shape
-        self.max_iter = max_iter = int(max_iter)
-        self.bv = eng.to_vec(b, m)
-        self.xt = None if x_true is None else eng.to_vec(x_true, n)
         x_start = eng.to_vec(x0, n)
-        self.hist = History(eng, history, max_iter, n, "CGLS xHistory")       # True / False / stride / 'host' / '<file>.npy'
-        self.keep = self.hist.keeps_any
-        self.X = self.hist.X
         # tol = 0 on a single rank: nothing needs ||x||, ||dx||, ||x-x_true|| before the end -> keep them as block
         # partials and sum all iterations in one launch afterwards (one reduction-finalize launch less per iteration)
         self.defer = bool(defer_norms) and eng.world == 1 and hasattr(eng, "cgls_update_deferred")
@@ -93,7 +64,6 @@ class CGLSRun:
         # scalar layout: S[0] = gamma_0 = ||t_0||^2 ; row k (1-based) at 5k: [delta, gamma, ||x||^2, ||dx||^2, ||x-xt||^2]
         self.S = S = eng.scalars(5 * (max_iter + 1))
         self.dist = eng.world > 1
-        self.k = 0
         # r = b - A x0 ; t = A^T r ; p = t                                                (CGLS.py:45-47)
         A.apply(x_start, out=self.r)
         eng.axpby(1.0, self.bv, -1.0, self.r, self.r)
@@ -101,35 +71,6 @@ class CGLSRun:
         eng.allreduce(S, 0, 1)
         self.p.copy_(self.t)
         self.x_cur = x_start
-
-    def slot(self, k):
-        """The device row holding iterate k (0-based)."""
-        return self.X[self.hist.slot(k)]
-
-    def step(self):
-        self._step()
-        self.hist.pushed(self.k - 1)
-
-    def _run_c_loop(self, n_steps, call):
-        """`call(k_first, n, X, keep)` enqueues n iterations writing iterate j (1-based) to X + (j-1) rows (keep) — all at
-        once, or, when the history is streamed through a ring of device slots, in chunks that stay inside one half of the
-        ring (the copies of one half drain while the other half is being written)."""
-        h = self.hist
-        if h.mode != "stream":
-            call(self.k + 1, n_steps, self.X, 1 if h.mode == "device" else 0)
-            self.k += n_steps
-        else:
-            while n_steps > 0:
-                k0 = self.k
-                c = min(n_steps, h.R // 2, h.R - k0 % h.R)
-                for j in range(c):
-                    h.row(k0 + j)                                  # the slots' previous copies must be out
-                call(k0 + 1, c, _ShiftedRows(self.X, k0 % h.R - k0), 1)
-                for j in range(c):
-                    h.pushed(k0 + j)
-                self.k += c
-                n_steps -= c
-        self.x_cur = self.slot(self.k - 1)
 
     def _step(self):
         eng, A, S = self.eng, self.A, self.S
@@ -170,36 +111,28 @@ class CGLSRun:
         eng.axpby(1.0, self.t, Coef(1.0, num=gamma, den=gamma_old), self.p, self.p)
         self.x_cur = x_new
 
-    def run(self, n_steps):
-        """Enqueue `n_steps` iterations.  With deferred norms on the HIP engine the whole stretch is one library call
-        (trk_cgls_iterate: the same launches as `step()`, driven from C instead of the interpreter)."""
-        n_steps = min(int(n_steps), self.max_iter - self.k)
-        if n_steps <= 0:
-            return
+    def _c_loop(self):
+        """With deferred norms on the HIP engine a whole stretch is one library call (trk_cgls_iterate: the same launches as
+        `step()`, driven from C instead of the interpreter)."""
         eng = self.eng
-        if self.defer and not self.dist and hasattr(self.A, "_h") and hasattr(eng, "cgls_iterate"):
-            def call(k_first, n, X, keep):
-                if self.recompute:
-                    self.n_np = eng.cgls_iterate_recompute(self.A._h, k_first, n, self.p, self.P_ring, self.x_batch, self.r, X,
-                                                           self.x_cur, self.xt, self.S.ref(0), self.NP.ref(0), 1024, self.n_np,
-                                                           self.PG.ref(0), self.PD.ref(0), self.PCAP)
-                    self.x_cur = _row_of(X, k_first + n - 2, keep)
-                    return
-                if self.x_batch > 1:
-                    self.n_np = eng.cgls_iterate_xbatch(self.A._h, k_first, n, self.p, self.P_ring, self.x_batch, self.r, self.t,
-                                                        self.w, X, self.x_cur, self.xt, self.S.ref(0), self.NP.ref(0), 1024,
-                                                        self.n_np, self.PG.ref(0), self.PD.ref(0), self.PCAP)
-                    self.x_cur = _row_of(X, k_first + n - 2, keep)
-                    return
+        if not (self.defer and not self.dist and hasattr(self.A, "_h") and hasattr(eng, "cgls_iterate")):
+            return None
+
+        def call(k_first, n, X, keep):
+            if self.recompute:
+                self.n_np = eng.cgls_iterate_recompute(self.A._h, k_first, n, self.p, self.P_ring, self.x_batch, self.r, X,
+                                                       self.x_cur, self.xt, self.S.ref(0), self.NP.ref(0), 1024, self.n_np,
+                                                       self.PG.ref(0), self.PD.ref(0), self.PCAP)
+            elif self.x_batch > 1:
+                self.n_np = eng.cgls_iterate_xbatch(self.A._h, k_first, n, self.p, self.P_ring, self.x_batch, self.r, self.t,
+                                                    self.w, X, self.x_cur, self.xt, self.S.ref(0), self.NP.ref(0), 1024,
+                                                    self.n_np, self.PG.ref(0), self.PD.ref(0), self.PCAP)
+            else:
                 self.n_np = eng.cgls_iterate(self.A._h, k_first, n, self.p, self.r, self.t, self.w, X, keep,
                                              self.x_cur, self.xt, self.S.ref(0), self.NP.ref(0), 1024, self.n_np,
                                              None if not self.raw else self.PG.ref(0), None if not self.raw else self.PD.ref(0),
                                              self.PCAP if self.raw else 0, self.grouping)
-                self.x_cur = _row_of(X, k_first + n - 2, keep)
-            self._run_c_loop(n_steps, call)
-        else:
-            for _ in range(n_steps):
-                self.step()
+        return call
 
     def row(self, k):
         """[delta, gamma, ||x||^2, ||dx||^2, ||x-xt||^2] of iteration k (host sync)."""
@@ -229,16 +162,10 @@ class CGLSRunSharded(CGLSRun):
     NPC = 1024
 
     def __init__(self, A, b, x0, max_iter, x_true=None, history=True):
-        self.A = A = as_operator(A)
-        self.eng = eng = A.engine
+        IterationRun.__init__(self, A, b, max_iter, x_true, history, "CGLS xHistory")
+        A, eng, max_iter = self.A, self.eng, self.max_iter
         m, n = A.shape
-        self.max_iter = max_iter = int(max_iter)
-        self.bv = eng.to_vec(b, m)
-        self.xt = None if x_true is None else eng.to_vec(x_true, n)
         x_start = eng.to_vec(x0, n)
-        self.hist = History(eng, history, max_iter, n, "CGLS xHistory")
-        self.keep = self.hist.keeps_any
-        self.X = self.hist.X
         self.defer, self.raw, self.grouping, self._final = False, False, 0, 0
         self.NP = eng.scalars(3 * self.NPC * max_iter)
         self.n_np = 0
@@ -246,7 +173,6 @@ class CGLSRunSharded(CGLSRun):
         self.S = eng.scalars(5 * (max_iter + 1))
         self.G = eng.scalars(4)                       # [gamma_{k-1}, ||q||^2, <q, w_{k-1}>, ||w_{k-1}||^2]: an iteration's one exchange
         self.dist = eng.world > 1
-        self.k = 0
         self.allreduces = 0
         self._rows = None
         # operators that can leave ||A^T r||^2 as raw block partials (the Radon projector, the blur): the kernel that forms the
@@ -286,26 +212,21 @@ class CGLSRunSharded(CGLSRun):
         self._adjoint()                                                      # t_k = A^T r_k, this rank's ||t_k||^2
         self.x_cur = x_new
 
-    def run(self, n_steps):
-        n_steps = min(int(n_steps), self.max_iter - self.k)
-        if n_steps <= 0:
-            return
+    def _c_loop(self):
         eng = self.eng
         comm_h = getattr(eng.comm, "_h", None) if self.dist else None       # libtrk's own communicator (dist.RcclComm)
-        if hasattr(eng, "cgls_iterate_sharded") and hasattr(self.A, "_h") and (not self.dist or comm_h is not None):
-            def call(k_first, n, X, keep):
-                self.n_np, self.n_g = eng.cgls_iterate_sharded(self.A._h, comm_h, k_first, n, self.p, self.r, self.t, self.q, self.w, X,
-                                                               keep, self.x_cur, self.xt, self.S.ref(0), self.G.ref(0), self.NP.ref(0),
-                                                               self.NPC, self.n_np, None if not self.rawg else self.PG.ref(0),
-                                                               self.PCAP if self.rawg else 0, self.n_g)
-                self.x_cur = _row_of(X, k_first + n - 2, keep)
-                eng.reduction_points += n
-                if self.dist:
-                    self.allreduces += n
-            self._run_c_loop(n_steps, call)
-        else:
-            for _ in range(n_steps):
-                self.step()
+        if not (hasattr(eng, "cgls_iterate_sharded") and hasattr(self.A, "_h") and (not self.dist or comm_h is not None)):
+            return None
+
+        def call(k_first, n, X, keep):
+            self.n_np, self.n_g = eng.cgls_iterate_sharded(self.A._h, comm_h, k_first, n, self.p, self.r, self.t, self.q, self.w, X,
+                                                           keep, self.x_cur, self.xt, self.S.ref(0), self.G.ref(0), self.NP.ref(0),
+                                                           self.NPC, self.n_np, None if not self.rawg else self.PG.ref(0),
+                                                           self.PCAP if self.rawg else 0, self.n_g)
+            eng.reduction_points += n
+            if self.dist:
+                self.allreduces += n
+        return call
 
     def rows(self):
         """(gamma_0, [delta, gamma, ||x||^2, ||dx||^2, ||x - x_true||^2] per iteration): the rank's norm shares are summed over
@@ -375,17 +296,11 @@ class CGLSRunFused(CGLSRun):
                 and eng.cgls_tiled_caps(A._h, 1024, cls.PCAP))
 
     def __init__(self, A, b, x0, max_iter, x_true=None, history=True, tiled=False):
-        self.A = A = as_operator(A)
-        self.eng = eng = A.engine
-        m, n = A.shape
         self.tiled = int(tiled)            # 0: streaming kernels; 1: tiled, four blurs per iteration; 2: tiled, two (w by recurrence)
-        self.max_iter = max_iter = int(max_iter)
-        self.bv = eng.to_vec(b, m)
-        self.xt = None if x_true is None else eng.to_vec(x_true, n)
+        IterationRun.__init__(self, A, b, max_iter, x_true, history, "CGLS xHistory")
+        A, eng, max_iter = self.A, self.eng, self.max_iter
+        m, n = A.shape
         x_start = eng.to_vec(x0, n)
-        self.hist = History(eng, history, max_iter, n, "CGLS xHistory")
-        self.keep = self.hist.keeps_any
-        self.X = self.hist.X
         self.R = eng.empty_basis(2, m)     # r ping-pong
         self.P = eng.empty_basis(2, n)     # p ping-pong
         if self.tiled != 2:                # (the two-blur tiled form does not read p or w in its first iteration)
@@ -397,7 +312,6 @@ class CGLSRunFused(CGLSRun):
         self.PD = uninit(self.PCAP)        # ||w||^2 partials (delta)
         self.NP = uninit(3 * 1024 * max_iter)        # norm partials of every iteration, summed once at the end
         self.dist = False
-        self.k = 0
         self.n_g = self.n_np = 0
         # r0 = b - A x0 ; t0 = A^T r0 with raw ||t0||^2 partials: K3 form with x1 = b, x2 = A x0, cb = -1
         A.apply(x_start, out=self.w)
@@ -446,21 +360,17 @@ class CGLSRunFused(CGLSRun):
                                                          self.S.ref(0), self.PG.ref(0), self.PD.ref(0), self.PCAP, self.NP.ref(0),
                                                          1024, self.n_g, self.n_np)
 
-    def run(self, n_steps):
-        """Enqueue `n_steps` iterations in one library call (trk_cgls_iterate_fused)."""
-        n_steps = min(int(n_steps), self.max_iter - self.k)
-        if n_steps <= 0:
-            return
+    def _c_loop(self):
+        """Always one library call (trk_cgls_iterate_fused, or the tiled forms)."""
+        if self.tiled:
+            return self._tiled_call
+
         def call(k_first, n, X, keep):
-            if self.tiled:
-                self._tiled_call(k_first, n, X, keep)
-            else:
-                self.n_g, self.n_np = self.eng.cgls_iterate_fused(self.A._h, k_first, n, self.P, self.R, self.t, self.w,
-                                                                  X, keep, self.x_cur, self.xt, self.S.ref(0),
-                                                                  self.PG.ref(0), self.PD.ref(0), self.PCAP, self.NP.ref(0), 1024,
-                                                                  self.n_g, self.n_np)
-            self.x_cur = _row_of(X, k_first + n - 2, keep)
-        self._run_c_loop(n_steps, call)
+            self.n_g, self.n_np = self.eng.cgls_iterate_fused(self.A._h, k_first, n, self.P, self.R, self.t, self.w,
+                                                              X, keep, self.x_cur, self.xt, self.S.ref(0),
+                                                              self.PG.ref(0), self.PD.ref(0), self.PCAP, self.NP.ref(0), 1024,
+                                                              self.n_g, self.n_np)
+        return call
 
     def _finish(self):
         """Sum the norm partials of all iterations (one launch) and the last gamma (one launch)."""

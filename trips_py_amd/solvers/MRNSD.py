@@ -11,14 +11,9 @@ Not built: sharded MRNSD, a periodic refresh of g from a true product, the s / r
 weighted or Poisson variants, box constraints (solvers.PDHG takes a box).
 """
 import numpy as np
-import torch
 
-from .._io import Formatter, History, as_operator
-from .CGLS import _ShiftedRows, _row_of
-
-
-def _host(v):
-    return v.detach().to("cpu").numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+from .._io import Formatter, _host, as_operator
+from ._run import IterationRun
 
 
 def default_x0(A, bv):
@@ -33,7 +28,7 @@ def default_x0(A, bv):
     return eng.to_vec(np.full(A.shape[1], c, dtype=np.float32))
 
 
-class MRNSDRun:
+class MRNSDRun(IterationRun):
     """The MRNSD recurrence as an object, like CGLSRun: `step()` enqueues one iteration from Python, `run(n)` n of them in one
     library call (trk_mrnsd_iterate: the same kernels, the same bits), `rows()` / `row(k)` download the scalars.
 
@@ -44,17 +39,13 @@ class MRNSDRun:
     CAP = 1024                             # blocks of a streaming kernel at most (gamma / bound / norm partials)
 
     def __init__(self, A, b, x0, max_iter, x_true=None, history=True):
-        self.A = A = as_operator(A)
-        self.eng = eng = A.engine
-        if eng.world > 1:
+        A = as_operator(A)
+        if A.engine.world > 1:
             raise NotImplementedError("MRNSD is not built for unknowns spread over ranks (eng.world > 1)")
+        super().__init__(A, b, max_iter, x_true, history, "MRNSD xHistory")
+        eng, max_iter = self.eng, self.max_iter
         m, n = A.shape
-        self.max_iter = max_iter = int(max_iter)
-        self.bv = eng.to_vec(b, m)
-        self.xt = None if x_true is None else eng.to_vec(x_true, n)
         x_start = default_x0(A, self.bv) if x0 is None else eng.to_vec(x0, n)
-        self.hist = History(eng, history, max_iter, n, "MRNSD xHistory")
-        self.X = self.hist.X
         self.g, self.s, self.z = eng.empty(n), eng.empty(n), eng.empty(n)
         self.r, self.u = eng.empty(m), eng.empty(m)
         self.S = S = eng.scalars(8 * (max_iter + 1))
@@ -63,7 +54,6 @@ class MRNSDRun:
         # operators that leave ||A s||^2 as raw block partials (the blur, the projectors): the update kernel adds them up itself
         self.raw = bool(hasattr(A, "_h") and hasattr(eng, "op_can_fuse") and eng.op_can_fuse(A._h))
         self.PU = eng.scalars(self.PCAP) if self.raw else None
-        self.k = 0
         self._final = 0
         # r = b - A x0 ; g = -A^T r ; s, gamma_0, bound_0, ||r_0||^2
         A.apply(x_start, out=self.r)
@@ -75,14 +65,10 @@ class MRNSDRun:
         self.NP = eng.scalars(4 * self.n_np * max(1, max_iter))
         self.x_cur = x_start
 
-    def slot(self, k):
-        """The device row holding iterate k (0-based)."""
-        return self.X[self.hist.slot(k)]
-
     def _half(self, k):
         return 2 * self.CAP * (k & 1)
 
-    def step(self):
+    def _step(self):
         eng, A, S = self.eng, self.A, self.S
         self.k += 1
         k = self.k
@@ -100,43 +86,18 @@ class MRNSDRun:
                                      self.g, self.s, self.z, self.r, self.u, self.xt, self.GB.ref(dst), self.CAP, S.ref(row),
                                      S.ref(0) if k == 1 else S.ref(row - 6), self.NP.ref(4 * self.n_np * (k - 1)), self.CAP)
         self.x_cur = x_new
-        self.hist.pushed(k - 1)
 
-    # the chunking of a streamed history: CGLSRun's
-    def _run_c_loop(self, n_steps, call):
-        h = self.hist
-        if h.mode != "stream":
-            call(self.k + 1, n_steps, self.X, 1 if h.mode == "device" else 0)
-            self.k += n_steps
-        else:
-            while n_steps > 0:
-                k0 = self.k
-                c = min(n_steps, h.R // 2, h.R - k0 % h.R)
-                for j in range(c):
-                    h.row(k0 + j)                                  # the slots' previous copies must be out
-                call(k0 + 1, c, _ShiftedRows(self.X, k0 % h.R - k0), 1)
-                for j in range(c):
-                    h.pushed(k0 + j)
-                self.k += c
-                n_steps -= c
-        self.x_cur = self.slot(self.k - 1)
-
-    def run(self, n_steps):
-        """Enqueue `n_steps` iterations: one library call on the HIP engine (trk_mrnsd_iterate), else `step()` by `step()`."""
-        n_steps = min(int(n_steps), self.max_iter - self.k)
-        if n_steps <= 0:
-            return
+    def _c_loop(self):
+        """One library call on the HIP engine (trk_mrnsd_iterate)."""
         eng = self.eng
-        if hasattr(self.A, "_h") and hasattr(eng, "mrnsd_iterate"):
-            def call(k_first, n, X, keep):
-                self.n_np = eng.mrnsd_iterate(self.A._h, k_first, n, self.g, self.s, self.z, self.r, self.u, X, keep, self.x_cur,
-                                              self.xt, self.S.ref(0), self.GB.ref(0), self.CAP, self.NP.ref(0), self.CAP, self.n_np,
-                                              None if not self.raw else self.PU.ref(0), self.PCAP if self.raw else 0)
-                self.x_cur = _row_of(X, k_first + n - 2, keep)
-            self._run_c_loop(n_steps, call)
-        else:
-            for _ in range(n_steps):
-                self.step()
+        if not (hasattr(self.A, "_h") and hasattr(eng, "mrnsd_iterate")):
+            return None
+
+        def call(k_first, n, X, keep):
+            self.n_np = eng.mrnsd_iterate(self.A._h, k_first, n, self.g, self.s, self.z, self.r, self.u, X, keep, self.x_cur,
+                                          self.xt, self.S.ref(0), self.GB.ref(0), self.CAP, self.NP.ref(0), self.CAP, self.n_np,
+                                          None if not self.raw else self.PU.ref(0), self.PCAP if self.raw else 0)
+        return call
 
     def _finish(self):
         """gamma_k, bound_k of the last iteration (still block partials) and the reported sums of every iteration into S."""

@@ -19,10 +19,9 @@ preconditioning or adaptive step balancing (`ratio` is the only knob), other dat
 """
 import numpy as np
 
-from .._io import Formatter, History, as_operator
+from .._io import Formatter, _host, as_operator
 from ..operators import operator_norm_sq
-from .CGLS import _row_of
-from .MRNSD import MRNSDRun, _host
+from ._run import IterationRun
 
 
 def _iso_geometry(L, tv, tv_dims):
@@ -55,7 +54,7 @@ def _iso_geometry(L, tv, tv_dims):
     return N, frames
 
 
-class PDHGRun:
+class PDHGRun(IterationRun):
     """The PDHG iteration as an object, like MRNSDRun: `step()` enqueues one iteration from Python, `run(n)` n of them in one library
     call when A and L both have handles (trk_pdhg_iterate: the same kernels, the same bits), `rows()` / `row(k)` download the sums.
 
@@ -67,10 +66,9 @@ class PDHGRun:
 
     def __init__(self, A, b, L, lam, sigma, tau, lower, upper, x0, max_iter, x_true=None, history=True, fused=None, tv="aniso",
                  tv_dims=None):
-        self.A = A = as_operator(A)
+        A = as_operator(A)
         self.L = L = as_operator(L, "L")
-        self.eng = eng = A.engine
-        if eng.world > 1:
+        if A.engine.world > 1:
             raise NotImplementedError("PDHG is not built for unknowns spread over ranks (eng.world > 1)")
         m, n = A.shape
         rows = L.shape[0]
@@ -86,9 +84,8 @@ class PDHGRun:
             raise ValueError("PDHG: need lower <= upper")
         self.tv = tv
         self.geo = _iso_geometry(L, tv, tv_dims)
-        self.max_iter = max_iter = int(max_iter)
-        self.bv = eng.to_vec(b, m)
-        self.xt = None if x_true is None else eng.to_vec(x_true, n)
+        super().__init__(A, b, max_iter, x_true, history, "PDHG xHistory")
+        eng, max_iter = self.eng, self.max_iter
         can = bool(hasattr(L, "_h") and hasattr(eng, "pdhg_fused_caps") and eng.pdhg_fused_caps(L._h))
         if self.geo is not None:                                   # the fused isotropic dual pairs the rows as its handle lays them out
             can = can and self.geo == (L.N, 1)
@@ -101,8 +98,6 @@ class PDHGRun:
             raise ValueError(f"x0 has {x0h.size} entries, expected {n}")
         self.x_cur = eng.to_vec(np.clip(x0h, np.float32(self.lo), np.float32(self.hi)))
         self.xbar = self.x_cur.clone()
-        self.hist = History(eng, history, max_iter, n, "PDHG xHistory")
-        self.X = self.hist.X
         self.p, self.w = eng.zeros(m), eng.empty(m)
         self.q, self.z = eng.zeros(rows), eng.empty(n)
         self.u, self.v = (None, None) if self.fused else (eng.empty(rows), eng.empty(n))
@@ -114,14 +109,9 @@ class PDHGRun:
         self.S = eng.scalars(8 * (max_iter + 1))
         self.B = eng.scalars(1)                                    # ||b||^2
         eng.nrm2sq(self.bv, self.B.ref(0))
-        self.k = 0
         self._final = 0
 
-    def slot(self, k):
-        """The device row holding iterate k (0-based)."""
-        return self.X[self.hist.slot(k)]
-
-    def step(self):
+    def _step(self):
         eng, A, L = self.eng, self.A, self.L
         self.k += 1
         k = self.k
@@ -142,7 +132,6 @@ class PDHGRun:
             L.apply(self.q, out=self.v, transpose=True)
             eng.pdhg_primal(self.tau, self.lo, self.hi, self.x_cur, self.z, self.v, x_new, self.xbar, self.xt, part, self.cap)
         self.x_cur = x_new
-        self.hist.pushed(k - 1)
 
     def _dual_q(self, u, q, part):
         if self.geo is None:
@@ -150,27 +139,21 @@ class PDHGRun:
         else:
             self.eng.pdhg_dual_q_iso(*self.geo, self.sigma, self.lam, u, q, part, self.cap)
 
-    _run_c_loop = MRNSDRun._run_c_loop                 # the chunking of a streamed history: CGLSRun's
-
-    def run(self, n_steps):
-        """Enqueue `n_steps` iterations: one library call where A and L both have handles, else `step()` by `step()`."""
-        n_steps = min(int(n_steps), self.max_iter - self.k)
-        if n_steps <= 0:
-            return
+    def _c_loop(self):
+        """One library call where A and L both have handles (trk_pdhg_iterate, trk_pdhg_iterate_iso)."""
         eng = self.eng
-        if hasattr(self.A, "_h") and hasattr(self.L, "_h") and hasattr(eng, "pdhg_iterate" if self.geo is None else "pdhg_iterate_iso"):
-            def call(k_first, n, X, keep):
-                rest = (k_first, n, self.sigma, self.tau, self.lam, self.lo, self.hi, self.fused, self.bv, self.p, self.q, self.w, self.u,
-                        self.z, self.v, X, keep, self.x_cur, self.xbar, self.xt, self.NP.ref(0), self.cap)
-                if self.geo is None:
-                    eng.pdhg_iterate(self.A._h, self.L._h, *rest)
-                else:
-                    eng.pdhg_iterate_iso(self.A._h, self.L._h, *self.geo, *rest)
-                self.x_cur = _row_of(X, k_first + n - 2, keep)
-            self._run_c_loop(n_steps, call)
-        else:
-            for _ in range(n_steps):
-                self.step()
+        if not (hasattr(self.A, "_h") and hasattr(self.L, "_h")
+                and hasattr(eng, "pdhg_iterate" if self.geo is None else "pdhg_iterate_iso")):
+            return None
+
+        def call(k_first, n, X, keep):
+            rest = (k_first, n, self.sigma, self.tau, self.lam, self.lo, self.hi, self.fused, self.bv, self.p, self.q, self.w, self.u,
+                    self.z, self.v, X, keep, self.x_cur, self.xbar, self.xt, self.NP.ref(0), self.cap)
+            if self.geo is None:
+                eng.pdhg_iterate(self.A._h, self.L._h, *rest)
+            else:
+                eng.pdhg_iterate_iso(self.A._h, self.L._h, *self.geo, *rest)
+        return call
 
     def _finish(self):
         """The block partials of the iterations not summed yet into their rows of S."""
