@@ -893,7 +893,17 @@ int trk_wgram_tv_z(const float* V, int64_t ld, int k, int N, const float* w, dou
 /* G[a][b] = sum_i w[i]^2 * W[a][i] * W[b][i]  (k x k, fp64, full symmetric; w may be NULL), and, if
  * b1 != NULL, c1[a] = sum_i w[i]*W[a][i]*b1[i], c2[a] = sum_i w[i]^2*W[a][i]*b1[i].
  * Replaces the from-scratch economic QR of AV*wf / LV*wr (MMGKS.py:58-59,94-95; GKS.py:54-56): the host
- * takes R = chol(G) and Q^T b = R^-T c. */
+ * takes R = chol(G) and Q^T b = R^-T c.
+ * ACCURACY, per entry, with u = 2^-24 and S = sum_i |w[i]^2 W[a][i] W[b][i]| (the sum of the entry's absolute terms; for c1, c2 the
+ * terms of the dot):
+ *   k + 2 <= 64 (k <= 64 without b1): matrix cores.  The weighted rows w W (and w b1) are rounded to fp32 once, their products are
+ *     formed and added in fp32 in groups of 32 consecutive elements, and every group's sum is added in fp64:
+ *     |G - exact| <= 36 u S  (2 u for the two operands, 32 u for the group's products and additions, the rest slack), the same for c1, c2.
+ *   beyond: w^2 and W w^2 are rounded to fp32, products and sums are fp64 throughout: |G - exact| <= 4 u S; c1, c2 are fp64 dots of W
+ *     with fl32(w b1), fl32(b1 fl32(w w)) (trk_gemv_t's bound, n 2^-53 S).
+ * G is exactly symmetric (G[a][b] and G[b][a] are one sum stored twice), the result does not depend on the call's history (fixed
+ * summation order), and operands for which every fp32 group sum is exact (e.g. dyadic data) give the exact G.  m = 0 gives zeros.
+ * Derivation and the entry-wise tests: tests/wgram_cases.py, tests/test_gpu_wgram_entrywise.py. */
 int trk_wgram(const float* W, int64_t ld, int k, int64_t m, const float* w, const float* b1, double* G_dev,
               double* c1_dev, double* c2_dev, trk_stream stream);
 
