@@ -4,7 +4,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 from trips_py_amd.operators import Radon2DParallel
 from trips_py_amd.solvers import Hybrid_LSQR
-HL = sys.modules["trips_py_amd.solvers.Hybrid_LSQR"]
+from trips_py_amd.solvers._worker import _Searcher
 from trips_py_amd import krylov
 N = 512
 R = Radon2DParallel(N, np.linspace(0, np.pi, 180, endpoint=False))
@@ -24,9 +24,9 @@ def wrap(obj, name, tag):
     setattr(obj, name, g)
 wrap(krylov.GKState, "absorb", "absorb (wait for the norms)")
 wrap(krylov.GKState, "step_prefetch", "step_prefetch (enqueue a step + download)")
-wrap(HL._Searcher, "collect", "collect lambda from the worker")
-wrap(HL._Searcher, "post_gcv", "post gcv search")
-wrap(HL._Searcher, "post_dp", "post dp search")
+wrap(_Searcher, "collect", "collect lambda from the worker")
+wrap(_Searcher, "post_gcv", "post gcv search")
+wrap(_Searcher, "post_dp", "post dp search")
 eng = R.engine
 wrap(type(eng), "bidiag_tikhonov", "bidiag_tikhonov")
 wrap(type(eng), "gemv_n_err", "gemv_n_err")
