@@ -378,8 +378,8 @@ int trk_gk_step_proj(trk_op* op, int k, const float* u_k, const float* v_prev, f
                      trk_stream stream);
 
 /* One fused CGLS vector update (CGLS.py:64-67):  step = *gamma / *delta ;
- *   x_new = x + step*p ; r = r - step*w ;  sums_dev[0] = ||x_new||^2, sums_dev[1] = ||step*p||^2
- *   (= ||x_new - x_old||^2, :76), sums_dev[2] = ||x_new - x_true||^2 if x_true != NULL (:79).
+ *   x_new = fmaf(step, p, x) ; r = fmaf(-step, w, r), step rounded to float and each update rounded ONCE ;  sums_dev[0] = ||x_new||^2,
+ *   sums_dev[1] = ||fl32(step*p)||^2 (the product rounded on its own: ||x_new - x_old||^2 of :76 up to that rounding), sums_dev[2] = ||x_new - x_true||^2 if x_true != NULL (:79).
  * x_new may alias x (in place) or be the next slot of an on-device history (xHistory, :66). */
 int trk_cgls_update_xr(int64_t n, int64_t m, const double* gamma_dev, const double* delta_dev, const float* x,
                        const float* p, float* x_new, float* r, const float* w, const float* x_true,
@@ -397,12 +397,12 @@ int trk_cgls_update_xr_src(int64_t n, int64_t m, const double* gamma, int gamma_
                            const float* x, const float* p, float* x_new, float* r, const float* w, const float* x_true,
                            double* publish_delta, double* norm_partials, int capacity_blocks, int* n_blocks,
                            trk_stream stream);
-/* p = t + (S(gamma_new) / *gamma_old) p  (CGLS.py:72; same arithmetic as trk_axpby) with gamma_new a scalar source; block 0
+/* p = fmaf((float)(S(gamma_new) / *gamma_old), p, t)  (CGLS.py:72; ONE rounding — trk_axpby rounds b p on its own) with gamma_new a scalar source; block 0
  * stores the finished gamma_new to *publish_gamma (may be NULL). */
 int trk_cgls_p_update(int64_t n, const float* t, float* p, const double* gamma_new, int gamma_new_n, const double* gamma_old,
                       double* publish_gamma, trk_stream stream);
 /* The two halves of the update regrouped so that p is read once: r -= (*gamma_old / S(delta)) w (block 0 publishes delta),
- * and, after t = A^T r: x_new = x + (*gamma_old / *delta) p together with p = t + (S(gamma_new) / *gamma_old) p (block 0
+ * and, after t = A^T r: x_new = fmaf((float)(*gamma_old / *delta), p, x) together with p = fmaf((float)(S(gamma_new) / *gamma_old), p, t) (block 0
  * publishes gamma_new; norms as trk_cgls_update_xr_deferred). */
 int trk_cgls_update_grouping(int64_t n);   /* 1: trk_cgls_iterate uses the r / xp grouping for vectors of n floats (measured rule) */
 int trk_cgls_r_update(int64_t m, const double* gamma_old, const double* delta, int delta_n, float* r, const float* w,
@@ -412,13 +412,13 @@ int trk_cgls_xp_update(int64_t n, const double* gamma_old, const double* delta, 
                        double* norm_partials, int capacity_blocks, int* n_blocks, trk_stream stream);
 /* Without a history x feeds nothing but the next x, so its update can wait: the directions of `count` iterations are kept and ONE pass
  * makes their x updates (count - 1 writes of x are not made; same fp32 operations in the same order, same bits).
- *   trk_cgls_p_update_to: trk_cgls_p_update with a destination, p_out = t + (S(gamma_new) / *gamma_old) p (p_out may be p).
+ *   trk_cgls_p_update_to: trk_cgls_p_update with a destination, p_out = fmaf((float)(S(gamma_new) / *gamma_old), p, t) (p_out may be p).
  *   trk_cgls_xs_update: iterations k_last - count + 1 .. k_last, 1 <= count <= 8.  Their directions sit in s_slots >= count slots used
  *   round-robin — slot 0 is p, slot j is ring + (j - 1) * ring_ld (ring may be NULL for s_slots = 1) — starting at slot `first`.
  *   x = x_{k_last - count}; x_new = x_{k_last} (may be x); every intermediate iterate is formed in registers and its three norms go
  *   to its own slice NP + 3 * *n_blocks * (j - 1), as trk_cgls_xp_update leaves them.  Step j is S[5(j-1)+1] / S[5j] (gamma_{j-1} /
- *   delta_j; S[0] for j = 1), finished scalars of the layout of trk_cgls_iterate.  p_out = t + (S(gamma_new) / gamma_{k_last - 1})
- *   p_{k_last} (may be any of the slots; fastest for what reads it next when it is p_{k_last}'s own); block 0 stores the finished
+ *   delta_j; S[0] for j = 1), finished scalars of the layout of trk_cgls_iterate.  p_out = fmaf(b, p_{k_last}, t), b = (float)(S(gamma_new) / gamma_{k_last - 1})
+ *   (may be any of the slots; fastest for what reads it next when it is p_{k_last}'s own); block 0 stores the finished
  *   gamma_new to S[5 k_last + 1].  All vectors 16-byte aligned.  Inputs that are not read again soon are loaded non-temporally (also
  *   by trk_cgls_p_update_to when p_out is not p). */
 int trk_cgls_p_update_to(int64_t n, const float* t, const float* p, float* p_out, const double* gamma_new, int gamma_new_n,
@@ -464,7 +464,7 @@ int trk_op_apply_sumsq_raw(trk_op* op, int transpose, const float* x, double* ys
 int trk_op_apply_ratio(trk_op* op, int transpose, const float* x, int coef_on_z, double sign, const double* num, int num_n,
                        const double* den, int den_n, const float* z, float* out, double* publish, int publish_den,
                        trk_stream stream);
-/* x_new = x + (S(gamma)/S(delta)) p (CGLS.py:64-65); block 0 stores the two finished scalars to publish_* (may be NULL);
+/* x_new = fmaf((float)(S(gamma)/S(delta)), p, x), one rounding (CGLS.py:64-65); block 0 stores the two finished scalars to publish_* (may be NULL);
  * [||x_new||^2, ||step*p||^2, ||x_new - x_true||^2] are left as *n_blocks x 3 raw partials (:76-80). */
 int trk_cgls_x_update(int64_t n, const double* gamma, int gamma_n, const double* delta, int delta_n, const float* x,
                       const float* p, float* x_new, const float* x_true, double* publish_delta, double* publish_gamma,

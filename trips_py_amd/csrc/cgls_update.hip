@@ -7,16 +7,25 @@ using namespace trk;
 namespace {
 
 // ------------------------------------------------------------------ one CGLS iterate step on values held in registers
-// d = step * p ; x' = x + d (x_step), and the iterate's three norms fed from x', d and x' - x_true (x_norms).  ONE definition for
-// k_cgls_xp_update and k_cgls_xs_update: the batched kernel has to leave the bits of the one-step kernel
+// x' = fl32(x + step * p): ONE rounding, fmaf(step, p, x) — and d = fl32(step * p), rounded on its own, for ||d||^2 alone (x' is NOT
+// x + d: the two differ in the last bit on about a fifth of general data).  The iterate's three norms are fed from x', d and
+// x' - x_true (x_norms).  Every kernel of this file forms x' this way, vector body and scalar tail alike, spelled fmaf so that the
+// compiler's contraction setting decides nothing (tests/test_gpu_vec_entrywise.py pins the form per kernel, body and tail).  ONE
+// definition for k_cgls_xp_update and k_cgls_xs_update: the batched kernel has to leave the bits of the one-step kernel
 // (tests/test_gpu_cgls_xbatch.py compares exactly).
+// d = fl32(step * p) on four lanes, as two packed products
+typedef float f2pk __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ float4 d_step4(float4 pv, float step) {
+  const f2pk lo = (f2pk){pv.x, pv.y} * step, hi = (f2pk){pv.z, pv.w} * step;
+  return make_float4(lo[0], lo[1], hi[0], hi[1]);
+}
 __device__ __forceinline__ float x_step(float x, float p, float step, float& d) {
   d = step * p;
-  return x + d;
+  return fmaf(step, p, x);
 }
 __device__ __forceinline__ float4 x_step4(float4 xv, float4 pv, float step, float4& d) {
-  d = make_float4(step * pv.x, step * pv.y, step * pv.z, step * pv.w);
-  return make_float4(xv.x + d.x, xv.y + d.y, xv.z + d.z, xv.w + d.w);
+  d = d_step4(pv, step);
+  return make_float4(fmaf(step, pv.x, xv.x), fmaf(step, pv.y, xv.y), fmaf(step, pv.z, xv.z), fmaf(step, pv.w, xv.w));
 }
 template <bool HAS_XT>
 __device__ __forceinline__ void x_norms(float xn, float d, float xt, double& s0, double& s1, double& s2) {
@@ -36,12 +45,15 @@ __device__ __forceinline__ void x_norms4(float4 xn, float4 d, float4 tt, double&
     s2 += e0 * e0 + e1 * e1 + e2 * e2 + e3 * e3;
   }
 }
+// p' = fl32(t + b * p): ONE rounding as well, fmaf(b, p, t) (trk_axpby(1, t, b, p) rounds b * p on its own)
+__device__ __forceinline__ float p_step(float t, float p, float b) { return fmaf(b, p, t); }
 __device__ __forceinline__ float4 p_step4(float4 tv, float4 pv, float b) {
-  return make_float4(fmaf(1.f, tv.x, b * pv.x), fmaf(1.f, tv.y, b * pv.y), fmaf(1.f, tv.z, b * pv.z), fmaf(1.f, tv.w, b * pv.w));
+  return make_float4(fmaf(b, pv.x, tv.x), fmaf(b, pv.y, tv.y), fmaf(b, pv.z, tv.z), fmaf(b, pv.w, tv.w));
 }
 
 // ------------------------------------------------------------------ fused CGLS update (CGLS.py:64-67,76,79)
-// partials layout: [block][3] = ||x_new||^2, ||step*p||^2, ||x_new - x_true||^2
+// x_new = fmaf(step, p, x) and r = fmaf(-step, w, r) with step = (float)(gamma / delta): one rounding each
+// partials layout: [block][3] = ||x_new||^2, ||fl32(step*p)||^2, ||x_new - x_true||^2
 template <bool HAS_XT, bool VEC>
 __global__ __launch_bounds__(NT) void k_cgls_update(int64_t n, int64_t m, ScalarSrc gamma, ScalarSrc delta,
                                                     const float* x, const float* p, float* x_new, float* r,
@@ -73,8 +85,8 @@ __global__ __launch_bounds__(NT) void k_cgls_update(int64_t n, int64_t m, Scalar
     mtail = m4 << 2;
     for (int64_t i = tid; i < n4; i += nth) {
       const float4 xv = ld4(x, i), pv = ld4(p, i);
-      const float4 d = make_float4(step * pv.x, step * pv.y, step * pv.z, step * pv.w);
-      const float4 xn = make_float4(xv.x + d.x, xv.y + d.y, xv.z + d.z, xv.w + d.w);
+      const float4 d = d_step4(pv, step);
+      const float4 xn = make_float4(fmaf(step, pv.x, xv.x), fmaf(step, pv.y, xv.y), fmaf(step, pv.z, xv.z), fmaf(step, pv.w, xv.w));
       if (nt & 2) st4_nt(x_new, i, xn); else st4(x_new, i, xn);
       s0 += (double)xn.x * xn.x + (double)xn.y * xn.y + (double)xn.z * xn.z + (double)xn.w * xn.w;
       s1 += (double)d.x * d.x + (double)d.y * d.y + (double)d.z * d.z + (double)d.w * d.w;
@@ -95,8 +107,8 @@ __global__ __launch_bounds__(NT) void k_cgls_update(int64_t n, int64_t m, Scalar
     }
   }
   for (int64_t i = ntail + tid; i < n; i += nth) {
-    const float d = step * p[i];
-    const float xn = x[i] + d;
+    const float pi = p[i], d = step * pi;
+    const float xn = fmaf(step, pi, x[i]);
     x_new[i] = xn;
     s0 += (double)xn * xn;
     s1 += (double)d * d;
@@ -117,8 +129,8 @@ __global__ __launch_bounds__(NT) void k_cgls_update(int64_t n, int64_t m, Scalar
 }
 
 // ------------------------------------------------------------------ CGLS direction update (CGLS.py:72)
-// p_out = t + (gamma_new / gamma_old) p with gamma_new possibly still the block partials of the adjoint kernel that produced
-// t; block 0 publishes the finished gamma_new.  Same arithmetic as trk_axpby(1, t, gamma_new/gamma_old, p).  p_out may be p.
+// p_out = fmaf(b, p, t), b = (float)(gamma_new / gamma_old), with gamma_new possibly still the block partials of the adjoint kernel that produced
+// t; block 0 publishes the finished gamma_new.  One rounding (trk_axpby(1, t, b, p) rounds b p on its own).  p_out may be p.
 // nt: bit 0 loads t, bit 1 loads p non-temporally — set when p_out is another buffer (the ring of trk_cgls_iterate_xbatch): neither
 // input is read again soon, and kept out of the caches they leave p_out there for the forward blur that follows (4096^2, s = 8: that
 // blur launch 26.3 -> 23.0 us, what it takes behind the in-place update; 7.68 k -> 7.82 k iterations/s, 5120^2 4.64 k -> 5.05 k).
@@ -145,7 +157,7 @@ __global__ __launch_bounds__(NT) void k_cgls_p_update(int64_t n, const float* __
       if (nt & 4) st4_nt(p_out, i, p_step4(v, w, b)); else st4(p_out, i, p_step4(v, w, b));
     }
   }
-  for (int64_t i = tail0 + tid; i < n; i += nth) p_out[i] = fmaf(1.f, t[i], b * p[i]);
+  for (int64_t i = tail0 + tid; i < n; i += nth) p_out[i] = p_step(t[i], p[i], b);
 }
 
 // ------------------------------------------------------------------ CGLS residual update alone (CGLS.py:67)
@@ -182,7 +194,7 @@ __global__ __launch_bounds__(NT) void k_cgls_r_update(int64_t m, const double* g
 }
 
 // ------------------------------------------------------------------ CGLS iterate + direction update in one pass over p
-// x_new = x + (gamma_old/delta) p (CGLS.py:64-65) and p = t + (S(gamma_new)/gamma_old) p (:72): p is read once for both
+// x_new = fmaf((float)(gamma_old/delta), p, x) (CGLS.py:64-65; one rounding) and p = fmaf((float)(S(gamma_new)/gamma_old), p, t) (:72): p is read once for both
 // (20n bytes instead of 12n + 12n); norms as k_cgls_update: [block][3] raw partials; block 0 publishes gamma_new.
 template <bool HAS_XT>
 __global__ __launch_bounds__(NT) void k_cgls_xp_update(int64_t n, const double* gold, const double* delta, ScalarSrc gnew,
@@ -217,7 +229,7 @@ __global__ __launch_bounds__(NT) void k_cgls_xp_update(int64_t n, const double* 
     float d;
     const float xn = x_step(x[i], pv, step, d);
     x_new[i] = xn;
-    p[i] = fmaf(1.f, t[i], b * pv);
+    p[i] = p_step(t[i], pv, b);
     x_norms<HAS_XT>(xn, d, HAS_XT ? x_true[i] : 0.f, s0, s1, s2);
   }
   s0 = block_sum<NT>(s0, lds);
@@ -235,7 +247,7 @@ __global__ __launch_bounds__(NT) void k_cgls_xp_update(int64_t n, const double* 
 // kept (trk_cgls_p_update_to writes each new one beside the old) and this kernel forms x_{k-C+1} .. x_k from x_{k-C} in registers —
 // the same fp32 operations in the same order as C launches of k_cgls_xp_update (x_step4) — accumulates the three norms of every one of
 // them and writes x ONCE: (C-1) of C writes of x are not made.  step_j = gamma_{j-1} / delta_j from the finished scalars in S (rows
-// k-C+1 .. k, all published by earlier launches); the direction update p_out = t + (S(gamma_new) / gamma_{k-1}) p_k and the published
+// k-C+1 .. k, all published by earlier launches); the direction update p_out = fmaf((float)(S(gamma_new) / gamma_{k-1}), p_k, t) and the published
 // gamma_k as k_cgls_xp_update.  Partials: iteration j's [block][3] at partials + (j - (k-C+1)) * slice.  x_new may be x and p_out any of
 // the directions (an element is read and then written by the same thread): no __restrict__ on them.
 // Cache hints of its own (bits beside those of stream_nontemporal(), set when C > 1): 256 = the directions before the last are loaded
@@ -320,7 +332,7 @@ __global__ __launch_bounds__(NT) void k_cgls_xs_update(int64_t n, const double* 
       x_norms<HAS_XT>(xv, d, tt, s0[c], s1[c], s2[c]);
     }
     x_new[i] = xv;
-    if (!XONLY) p_out[i] = fmaf(1.f, tv, b * pv[C - 1]);
+    if (!XONLY) p_out[i] = p_step(tv, pv[C - 1], b);
   }
 #pragma unroll
   for (int c = 0; c < C; ++c) {
@@ -336,7 +348,7 @@ __global__ __launch_bounds__(NT) void k_cgls_xs_update(int64_t n, const double* 
 }
 
 // ------------------------------------------------------------------ CGLS x-update of the fused fast path
-// x_new = x + (gamma/delta) p with gamma, delta possibly still block partials of the producing blur kernels; block 0
+// x_new = fmaf((float)(gamma/delta), p, x) (one rounding) with gamma, delta possibly still block partials of the producing blur kernels; block 0
 // publishes the two finished scalars; the three norms are left as raw partials [block][3] (summed once, after the solve).
 template <bool HAS_XT>
 __global__ __launch_bounds__(NT) void k_cgls_x_update(int64_t n, ScalarSrc gamma, ScalarSrc delta, const float* __restrict__ x,
@@ -363,8 +375,8 @@ __global__ __launch_bounds__(NT) void k_cgls_x_update(int64_t n, ScalarSrc gamma
   const int64_t n4 = n >> 2;
   for (int64_t i = tid; i < n4; i += nth) {
     const float4 xv = ld4(x, i), pv = ld4(p, i);
-    const float4 d = make_float4(step * pv.x, step * pv.y, step * pv.z, step * pv.w);
-    const float4 xn = make_float4(xv.x + d.x, xv.y + d.y, xv.z + d.z, xv.w + d.w);
+    const float4 d = d_step4(pv, step);
+    const float4 xn = make_float4(fmaf(step, pv.x, xv.x), fmaf(step, pv.y, xv.y), fmaf(step, pv.z, xv.z), fmaf(step, pv.w, xv.w));
     st4(x_new, i, xn);
     s0 += (double)xn.x * xn.x + (double)xn.y * xn.y + (double)xn.z * xn.z + (double)xn.w * xn.w;
     s1 += (double)d.x * d.x + (double)d.y * d.y + (double)d.z * d.z + (double)d.w * d.w;
@@ -375,8 +387,8 @@ __global__ __launch_bounds__(NT) void k_cgls_x_update(int64_t n, ScalarSrc gamma
     }
   }
   for (int64_t i = (n4 << 2) + tid; i < n; i += nth) {
-    const float d = step * p[i];
-    const float xn = x[i] + d;
+    const float pi = p[i], d = step * pi;
+    const float xn = fmaf(step, pi, x[i]);
     x_new[i] = xn;
     s0 += (double)xn * xn;
     s1 += (double)d * d;
