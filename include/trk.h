@@ -721,7 +721,40 @@ int trk_mrnsd_iterate(trk_op* A, int k_first, int n_iters, float* g, float* s, f
  *   handle's product.  trk_pdhg_tv_primal follows it unchanged (the primal is linear in q).
  * trk_pdhg_blocks_iso: trk_pdhg_blocks for the isotropic forms (L_fused NULL: grouped blocks + tail blocks count for the dual).
  * trk_pdhg_iterate_iso: trk_pdhg_iterate with the geometry.  Five launches with `fused` (then (N, frames) must be the handle's
- *   (N, 1)), seven without a tail and eight with one.  L must be rows x frames N^2 with rows >= frames 2 N (N - 1). */
+ *   (N, 1)), seven without a tail and eight with one.  L must be rows x frames N^2 with rows >= frames 2 N (N - 1).
+ *
+ * ISOTROPIC SPACE-TIME TV (the *_iso3 entry points): lam sum over voxels of sqrt(h^2 + v^2 + t^2), one group per voxel of a 2-D +
+ * time volume, on the row layout of trk_spacetime_create with every frame on one rank: `frames` blocks [H_t ; V_t] as above, then
+ * the (frames - 1) N^2 temporal rows T_t = x_t - x_{t+1}.  rows must be frames 2 N (N - 1) + (frames - 1) N^2 EXACTLY (no further
+ * tail) and L rows x frames N^2.  The group of voxel (t, i, j) holds whichever of H_t[i][j] (j < N - 1), V_t[i][j] (i < N - 1) and
+ * T_t[i][j] (t < frames - 1) exist:
+ *   triple:  all three
+ *   pair:    (h, v) on the last frame, (h, t) on the last image row, (v, t) on the last image column: the pair's operations above,
+ *            the members in row order (h before v before t)
+ *   single:  the one row of a voxel on two of those faces: the dual q entry, bit for bit; voxel (frames-1, N-1, N-1) has no row
+ * The fp32 operations of a triple, in this order (sqrtf and / correctly rounded, nothing contracted but the fmaf written out):
+ *   th = fmaf(sf, uh, qh) ;  tv = fmaf(sf, uv, qv) ;  tt = fmaf(sf, ut, qt)
+ *   m2 = fmaf(th, th, fmaf(tv, tv, tt * tt)) ;  m = sqrtf(m2)
+ *   if (m <= lf) { q' = t }  else { s = lf / m ;  qh' = th * s ;  qv' = tv * s ;  qt' = tt * s }
+ * Slot 1 takes sqrt((double)uh * uh + (double)uv * uv + (double)ut * ut) per triple; slot 3 stays ||q' - q||^2.  With frames = 1
+ * every group is a pair or a single of the isotropic term above: the same bits as the *_iso entry points.
+ * Bound on a projected triple (no underflow, eps = 2^-24): m2 carries three roundings of non-negative terms, so m2 >= |t|^2 (1 - eps)^3
+ * and m >= |t| (1 - eps)^2.5; s <= (lf / m)(1 + eps) and each member of q' carries one more rounding, so the float64 norm of q' is
+ * at most lf (1 + eps)^2 / (1 - eps)^2.5 = lf (1 + 4.5 eps + O(eps^2)).  (A pair: 4 eps.)  The tests allow 8 eps.
+ * trk_pdhg_dual_q_iso3: u = L xbar in memory, any L with that row layout; ONE launch over (column blocks, row batches, frames), one
+ *   thread per image column holding every member of its voxels' groups.
+ * trk_pdhg_st_dual_iso3, trk_pdhg_st_primal: the fused forms for a handle from trk_spacetime_create.  The dual reads xbar_t (the
+ *   column, its right neighbour, the row below) and xbar_{t+1} and forms h = xbar[i][j] - xbar[i][j+1], v = xbar[i][j] - xbar[i+1][j],
+ *   t = xbar_t[i][j] - xbar_{t+1}[i][j] in registers; the primal gathers L^T q per voxel as 0, + H[i][j], - H[i][j-1], + V[i][j],
+ *   - V[i-1][j], + T_t, - T_{t-1}, absent terms skipped (the operator's own transpose), and knows nothing of the grouping.  The same
+ *   entries in the same order as trk_pdhg_dual_q_iso3 and trk_pdhg_primal on that handle's products: the same bits in q, x', xbar'.
+ *   A time-sharded handle (has_next / has_prev) and any other handle: TRK_EUNSUPPORTED, before anything else is looked at.
+ *   trk_pdhg_fused_caps stays 0 for a space-time handle: it speaks for trk_pdhg_tv_dual / _iso / _primal only.
+ *   The three kernels share one grid of at most max(4096, column blocks x frames) blocks (a block strides over row batches) and write
+ *   disjoint slots of partial row (z gridDim.y + y) gridDim.x + x.
+ * trk_pdhg_blocks_iso3: trk_pdhg_blocks for these forms; L_fused must be such a handle (TRK_EUNSUPPORTED) of geometry (N, frames)
+ *   (TRK_EINVAL).
+ * trk_pdhg_iterate_iso3: trk_pdhg_iterate_iso's arguments.  Five launches with `fused`, eight without. */
 int trk_pdhg_blocks(int64_t m, int64_t n, int64_t rows, const trk_op* L_fused, int* blocks);
 int trk_pdhg_dual_p(int64_t m, double sigma, const float* w, const float* b, float* p, double* partials, int capacity_blocks,
                     int* n_blocks, trk_stream stream);
@@ -747,6 +780,17 @@ int trk_pdhg_iterate_iso(trk_op* A, trk_op* L, int N, int frames, int k_first, i
                          double lo, double hi, int fused, const float* b, float* p, float* q, float* w, float* u, float* z, float* v,
                          float* X, int64_t x_ld, int keep_history, const float* x_prev, float* xbar, const float* x_true, double* NP,
                          int np_capacity_blocks, trk_stream stream);
+int trk_pdhg_blocks_iso3(int64_t m, int64_t n, int64_t rows, int N, int frames, const trk_op* L_fused, int* blocks);
+int trk_pdhg_dual_q_iso3(int N, int frames, int64_t rows, double sigma, double lam, const float* u, float* q, double* partials,
+                         int capacity_blocks, int* n_blocks, trk_stream stream);
+int trk_pdhg_st_dual_iso3(trk_op* L, double sigma, double lam, const float* xbar, float* q, double* partials, int capacity_blocks,
+                          int* n_blocks, trk_stream stream);
+int trk_pdhg_st_primal(trk_op* L, double tau, double lo, double hi, const float* x, const float* z, const float* q, float* x_new,
+                       float* xbar, const float* x_true, double* partials, int capacity_blocks, int* n_blocks, trk_stream stream);
+int trk_pdhg_iterate_iso3(trk_op* A, trk_op* L, int N, int frames, int k_first, int n_iters, double sigma, double tau, double lam,
+                          double lo, double hi, int fused, const float* b, float* p, float* q, float* w, float* u, float* z, float* v,
+                          float* X, int64_t x_ld, int keep_history, const float* x_prev, float* xbar, const float* x_true, double* NP,
+                          int np_capacity_blocks, trk_stream stream);
 
 /* ---------------------------------------------------------------- tall-skinny basis ops */
 /* h[j] = sum_i w2[i] * V[j][i] * r[i], j < k  (w2 may be NULL = 1).  One pass over V.

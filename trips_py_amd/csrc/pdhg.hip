@@ -7,6 +7,8 @@
 // Isotropic TV (the *_iso entry points): lam sum_g ||(L x)_g||_2 with the groups of a geometry (N, frames) on the first-difference
 // row layout (include/trk.h); q' = every group of q + sig u projected onto the 2-norm ball of radius lam, everything else unchanged.
 // The grouped rows run on k_pdhg_dual_q_iso (tvops.hip: the column-thread layout), the tail rows on k_pdhg_dual_q below.
+// Isotropic space-time TV (the *_iso3 entry points): the groups (h, v, t) of a voxel on the space-time row layout, one kernel
+// (k_pdhg_dual_q_iso3) or, on the space-time handle, the fused pair k_pdhg_st_dual_iso3 / k_pdhg_st_primal of tvops.hip.
 // sig, tau, lam, lo, hi are host constants: nothing is read back inside the loop and trk_pdhg_iterate enqueues a whole solve.
 // The three streaming kernels are here; the fused forms for the 2-D first differences (no vector of the length of L xbar or L^T q
 // in memory) are in tvops.hip and share one entry (pdhg_internal.h).  Vectors fp32, sums fp64 block partials, no atomics: every
@@ -126,20 +128,32 @@ inline bool finite_pos(double v) { return v > 0.0 && v < __builtin_inf(); }
 // the rows [H ; V] of `frames` N x N images: where the tail of an isotropic L begins
 inline int64_t iso_grouped_rows(int N, int frames) { return (int64_t)frames * 2 * N * (N - 1); }
 
-// The loop of trk_pdhg_iterate (N = 0: the l1 term, every row of L a group of its own) and of trk_pdhg_iterate_iso (N >= 2: the
-// isotropic groups of geometry (N, frames)).  Only the dual update of q differs.
-int pdhg_iterate(const char* who, trk_op* A, trk_op* L, int N, int frames, int k_first, int n_iters, double sigma, double tau, double lam,
-                 double lo, double hi, int fused, const float* b, float* p, float* q, float* w, float* u, float* z, float* v, float* X,
-                 int64_t x_ld, int keep_history, const float* x_prev, float* xbar, const float* x_true, double* NP,
+// the rows of the space-time operator of `frames` N x N images: the grouped rows, then the (frames - 1) N^2 temporal rows
+inline int64_t iso3_rows(int N, int frames) { return iso_grouped_rows(N, frames) + (int64_t)(frames - 1) * N * N; }
+
+// How the rows of L are grouped in the dual update of q: every row alone (the l1 term), the pairs (h, v) of a pixel, or the
+// groups (h, v, t) of a voxel.
+enum class Groups { kRows, kIso, kIso3 };
+
+// The loop of trk_pdhg_iterate, trk_pdhg_iterate_iso and trk_pdhg_iterate_iso3 (the groups of geometry (N, frames)).  Only the
+// dual update of q differs, and with `fused` the handle the two fused kernels belong to.
+int pdhg_iterate(const char* who, trk_op* A, trk_op* L, Groups groups, int N, int frames, int k_first, int n_iters, double sigma,
+                 double tau, double lam, double lo, double hi, int fused, const float* b, float* p, float* q, float* w, float* u, float* z,
+                 float* v, float* X, int64_t x_ld, int keep_history, const float* x_prev, float* xbar, const float* x_true, double* NP,
                  int np_capacity_blocks, trk_stream stream) {
-  const bool iso = N > 0;
+  const bool iso = groups == Groups::kIso, iso3 = groups == Groups::kIso3;
   TRK_REQUIRE(A && L && b && p && q && w && z && X && x_prev && xbar && NP, "%s: NULL argument", who);
   TRK_REQUIRE(fused || (u && v), "%s: the generic path needs u and v", who);
   TRK_REQUIRE(k_first >= 1 && n_iters >= 0, "%s: need k_first >= 1, n_iters >= 0", who);
   TRK_REQUIRE(L->cols == A->cols, "%s: A and L must have the same number of columns", who);
   const int64_t m = A->rows, n = A->cols, rows = L->rows;
   int need = 0;
-  if (iso) {
+  if (iso3) {
+    TRK_REQUIRE(rows == iso3_rows(N, frames) && n == (int64_t)frames * N * N,
+                "%s: L is %lld x %lld, not the space-time first differences of %d images of %d x %d", who, (long long)rows, (long long)n,
+                frames, N, N);
+    if (int rc = trk_pdhg_blocks_iso3(m, n, rows, N, frames, fused ? L : nullptr, &need)) return rc;  // TRK_EUNSUPPORTED: no fused form
+  } else if (iso) {
     TRK_REQUIRE(rows >= iso_grouped_rows(N, frames) && n == (int64_t)frames * N * N,
                 "%s: L is %lld x %lld, not the first differences of %d images of %d x %d (and a tail)", who, (long long)rows,
                 (long long)n, frames, N, N);
@@ -157,17 +171,20 @@ int pdhg_iterate(const char* who, trk_op* A, trk_op* L, int N, int frames, int k
     if ((rc = trk_op_apply(A, 0, xbar, 0, w, 0, 1, nullptr, stream))) return rc;                       // w = A xbar
     if ((rc = trk_pdhg_dual_p(m, sigma, w, b, p, part, np_capacity_blocks, &nb, stream))) return rc;
     if (fused) {
-      rc = iso ? trk_pdhg_tv_dual_iso(L, sigma, lam, xbar, q, part, np_capacity_blocks, &nb, stream)
-               : trk_pdhg_tv_dual(L, sigma, lam, xbar, q, part, np_capacity_blocks, &nb, stream);
+      rc = iso3  ? trk_pdhg_st_dual_iso3(L, sigma, lam, xbar, q, part, np_capacity_blocks, &nb, stream)
+           : iso ? trk_pdhg_tv_dual_iso(L, sigma, lam, xbar, q, part, np_capacity_blocks, &nb, stream)
+                 : trk_pdhg_tv_dual(L, sigma, lam, xbar, q, part, np_capacity_blocks, &nb, stream);
     } else {
       if ((rc = trk_op_apply(L, 0, xbar, 0, u, 0, 1, nullptr, stream))) return rc;                     // u = L xbar
-      rc = iso ? trk_pdhg_dual_q_iso(N, frames, rows, sigma, lam, u, q, part, np_capacity_blocks, &nb, stream)
-               : trk_pdhg_dual_q(rows, sigma, lam, u, q, part, np_capacity_blocks, &nb, stream);
+      rc = iso3  ? trk_pdhg_dual_q_iso3(N, frames, rows, sigma, lam, u, q, part, np_capacity_blocks, &nb, stream)
+           : iso ? trk_pdhg_dual_q_iso(N, frames, rows, sigma, lam, u, q, part, np_capacity_blocks, &nb, stream)
+                 : trk_pdhg_dual_q(rows, sigma, lam, u, q, part, np_capacity_blocks, &nb, stream);
     }
     if (rc) return rc;
     if ((rc = trk_op_apply(A, 1, p, 0, z, 0, 1, nullptr, stream))) return rc;                          // z = A^T p'
     if (fused) {
-      rc = trk_pdhg_tv_primal(L, tau, lo, hi, x_prev, z, q, x_new, xbar, x_true, part, np_capacity_blocks, &nb, stream);
+      rc = iso3 ? trk_pdhg_st_primal(L, tau, lo, hi, x_prev, z, q, x_new, xbar, x_true, part, np_capacity_blocks, &nb, stream)
+                : trk_pdhg_tv_primal(L, tau, lo, hi, x_prev, z, q, x_new, xbar, x_true, part, np_capacity_blocks, &nb, stream);
     } else {
       if ((rc = trk_op_apply(L, 1, q, 0, v, 0, 1, nullptr, stream))) return rc;                        // v = L^T q'
       rc = trk_pdhg_primal(n, tau, lo, hi, x_prev, z, v, x_new, xbar, x_true, part, np_capacity_blocks, &nb, stream);
@@ -294,8 +311,8 @@ int trk_pdhg_iterate(trk_op* A, trk_op* L, int k_first, int n_iters, double sigm
                      int fused, const float* b, float* p, float* q, float* w, float* u, float* z, float* v, float* X, int64_t x_ld,
                      int keep_history, const float* x_prev, float* xbar, const float* x_true, double* NP, int np_capacity_blocks,
                      trk_stream stream) {
-  return pdhg_iterate("trk_pdhg_iterate", A, L, 0, 0, k_first, n_iters, sigma, tau, lam, lo, hi, fused, b, p, q, w, u, z, v, X, x_ld,
-                      keep_history, x_prev, xbar, x_true, NP, np_capacity_blocks, stream);
+  return pdhg_iterate("trk_pdhg_iterate", A, L, Groups::kRows, 0, 0, k_first, n_iters, sigma, tau, lam, lo, hi, fused, b, p, q, w, u, z, v, X,
+                      x_ld, keep_history, x_prev, xbar, x_true, NP, np_capacity_blocks, stream);
 }
 
 int trk_pdhg_iterate_iso(trk_op* A, trk_op* L, int N, int frames, int k_first, int n_iters, double sigma, double tau, double lam,
@@ -303,8 +320,53 @@ int trk_pdhg_iterate_iso(trk_op* A, trk_op* L, int N, int frames, int k_first, i
                          float* X, int64_t x_ld, int keep_history, const float* x_prev, float* xbar, const float* x_true, double* NP,
                          int np_capacity_blocks, trk_stream stream) {
   TRK_REQUIRE(N >= 2 && frames >= 1, "trk_pdhg_iterate_iso: need N >= 2, frames >= 1");
-  return pdhg_iterate("trk_pdhg_iterate_iso", A, L, N, frames, k_first, n_iters, sigma, tau, lam, lo, hi, fused, b, p, q, w, u, z, v, X,
-                      x_ld, keep_history, x_prev, xbar, x_true, NP, np_capacity_blocks, stream);
+  return pdhg_iterate("trk_pdhg_iterate_iso", A, L, Groups::kIso, N, frames, k_first, n_iters, sigma, tau, lam, lo, hi, fused, b, p, q, w, u, z,
+                      v, X, x_ld, keep_history, x_prev, xbar, x_true, NP, np_capacity_blocks, stream);
+}
+
+int trk_pdhg_blocks_iso3(int64_t m, int64_t n, int64_t rows, int N, int frames, const trk_op* L_fused, int* blocks) {
+  TRK_REQUIRE(blocks && m >= 1 && n >= 1 && rows >= 1, "trk_pdhg_blocks_iso3: need m, n, rows >= 1");
+  TRK_REQUIRE(N >= 2 && frames >= 1 && frames <= 65535, "trk_pdhg_blocks_iso3: need N >= 2, 1 <= frames <= 65535");
+  TRK_REQUIRE(rows == iso3_rows(N, frames),
+              "trk_pdhg_blocks_iso3: %lld rows are not the %lld of the space-time differences of %d images of %d x %d", (long long)rows,
+              (long long)iso3_rows(N, frames), frames, N, N);
+  if (L_fused) {
+    int hN = 0, hf = 0;
+    if (!pdhg_st_geometry(L_fused, &hN, &hf))
+      return fail(TRK_EUNSUPPORTED,
+                  "trk_pdhg_blocks_iso3: the fused space-time forms take a handle from trk_spacetime_create with every frame on one rank");
+    TRK_REQUIRE(hN == N && hf == frames, "trk_pdhg_blocks_iso3: the fused forms take the geometry of their handle, (%d, %d)", hN, hf);
+  }
+  const int g = stream_grid(m > n ? m : n), t = pdhg_iso3_blocks(N, frames);   // the fused and the unfused dual share one grid
+  *blocks = t > g ? t : g;
+  return TRK_OK;
+}
+
+int trk_pdhg_dual_q_iso3(int N, int frames, int64_t rows, double sigma, double lam, const float* u, float* q, double* partials,
+                         int capacity_blocks, int* n_blocks, trk_stream st) {
+  TRK_REQUIRE(u && q && partials && n_blocks, "trk_pdhg_dual_q_iso3: NULL argument");
+  TRK_REQUIRE(N >= 2 && frames >= 1 && frames <= 65535, "trk_pdhg_dual_q_iso3: need N >= 2, 1 <= frames <= 65535");
+  TRK_REQUIRE(rows == iso3_rows(N, frames),
+              "trk_pdhg_dual_q_iso3: %lld rows are not the %lld of the space-time differences of %d images of %d x %d", (long long)rows,
+              (long long)iso3_rows(N, frames), frames, N, N);
+  TRK_REQUIRE(finite_pos(sigma), "trk_pdhg_dual_q_iso3: sigma must be finite and > 0");
+  TRK_REQUIRE(lam >= 0.0 && lam < __builtin_inf(), "trk_pdhg_dual_q_iso3: lam must be finite and >= 0");
+  TRK_REQUIRE(q != u, "trk_pdhg_dual_q_iso3: q must not alias u");
+  const int nb = pdhg_iso3_blocks(N, frames);
+  TRK_REQUIRE(nb <= capacity_blocks, "trk_pdhg_dual_q_iso3: partial buffer too small (%d blocks needed)", nb);
+  *n_blocks = nb;
+  pdhg_dual_q_iso3_launch(N, frames, (float)sigma, (float)lam, u, q, partials, (hipStream_t)st);
+  TRK_LAUNCH_CHECK();
+  return TRK_OK;
+}
+
+int trk_pdhg_iterate_iso3(trk_op* A, trk_op* L, int N, int frames, int k_first, int n_iters, double sigma, double tau, double lam,
+                          double lo, double hi, int fused, const float* b, float* p, float* q, float* w, float* u, float* z, float* v,
+                          float* X, int64_t x_ld, int keep_history, const float* x_prev, float* xbar, const float* x_true, double* NP,
+                          int np_capacity_blocks, trk_stream stream) {
+  TRK_REQUIRE(N >= 2 && frames >= 1, "trk_pdhg_iterate_iso3: need N >= 2, frames >= 1");
+  return pdhg_iterate("trk_pdhg_iterate_iso3", A, L, Groups::kIso3, N, frames, k_first, n_iters, sigma, tau, lam, lo, hi, fused, b, p, q, w,
+                      u, z, v, X, x_ld, keep_history, x_prev, xbar, x_true, NP, np_capacity_blocks, stream);
 }
 
 }  // extern "C"

@@ -50,6 +50,30 @@ __device__ __forceinline__ void pdhg_q_pair(float sig, float lam, float uh, floa
   qv = nv;
 }
 
+// dual of the regulariser, isotropic in space and time: the H, V and T entry of one voxel are projected together.
+//   th = fmaf(sig, uh, qh) ; tv = fmaf(sig, uv, qv) ; tt = fmaf(sig, ut, qt) ; m = sqrtf(fmaf(th, th, fmaf(tv, tv, tt * tt)))
+//   m <= lam: q' = t ; else s = lam / m, q' = t * s          (lam = 0: as the pair)
+//   s1 += sqrt(uh^2 + uv^2 + ut^2) ; s3 += (qh' - qh)^2 + (qv' - qv)^2 + (qt' - qt)^2     (fp64 from the fp32 values)
+__device__ __forceinline__ void pdhg_q_triple(float sig, float lam, float uh, float uv, float ut, float& qh, float& qv, float& qt,
+                                              double& s1, double& s3) {
+#pragma clang fp contract(off)
+  const float th = fmaf(sig, uh, qh), tv = fmaf(sig, uv, qv), tt = fmaf(sig, ut, qt);
+  const float m = sqrtf(fmaf(th, th, fmaf(tv, tv, tt * tt)));
+  float nh = th, nv = tv, nt = tt;
+  if (!(m <= lam)) {
+    const float s = lam / m;
+    nh = th * s;
+    nv = tv * s;
+    nt = tt * s;
+  }
+  const double dh = (double)nh - (double)qh, dv = (double)nv - (double)qv, dt = (double)nt - (double)qt;
+  s1 += sqrt((double)uh * (double)uh + (double)uv * (double)uv + (double)ut * (double)ut);
+  s3 += dh * dh + dv * dv + dt * dt;
+  qh = nh;
+  qv = nv;
+  qt = nt;
+}
+
 // primal: g = z + v (formed by the caller) ; x' = clip(fmaf(-tau, g, x), lo, hi) ; xbar' = fmaf(2, x', -x) ; d = x' - x
 // s4 += x'^2, s5 += d^2, s6 += (x' - x_true)^2, s7 += 1 where x' sits on a bound
 template <bool HAS_XT>
@@ -77,5 +101,12 @@ int pdhg_tv_size(const trk_op* L);
 // writes (slots 1 and 3 of rows 0 .. blocks - 1).
 int pdhg_iso_blocks(int N, int frames);
 void pdhg_dual_q_iso_launch(int N, int frames, float sig, float lam, const float* u, float* q, double* partials, hipStream_t s);
+// tvops.hip: the space-time groups (h, v, t) of geometry (N, frames).  pdhg_iso3_blocks: the blocks (= rows of 8 partials) of ONE
+// launch over all frames, which the unfused dual, the fused dual and the fused primal share.  pdhg_dual_q_iso3_launch: the unfused
+// dual on u and q of frames 2 N (N - 1) + (frames - 1) N^2 rows, slots 1 and 3 of rows 0 .. blocks - 1.
+int pdhg_iso3_blocks(int N, int frames);
+void pdhg_dual_q_iso3_launch(int N, int frames, float sig, float lam, const float* u, float* q, double* partials, hipStream_t s);
+// tvops.hip: 1 and (N, frames) for a space-time handle whose frames all lie on this rank, 0 for any other handle
+int pdhg_st_geometry(const trk_op* L, int* N, int* frames);
 
 }  // namespace trk

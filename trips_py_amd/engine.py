@@ -811,6 +811,50 @@ class HipEngine:
                                            int(np_cap), self.stream())
         _lib.check(rc, "trk_pdhg_iterate_iso")
 
+    # isotropic space-time TV: the groups (h, v, t) of geometry (N, frames) on the space-time row layout (include/trk.h)
+    def pdhg_blocks_iso3(self, m, n, rows, N, frames, fused_handle=None):
+        """pdhg_blocks for the space-time groups."""
+        c = ctypes.c_int(0)
+        _lib.check(self.lib.trk_pdhg_blocks_iso3(int(m), int(n), int(rows), int(N), int(frames), fused_handle, ctypes.byref(c)),
+                   "trk_pdhg_blocks_iso3")
+        return c.value
+
+    def pdhg_dual_q_iso3(self, N, frames, sigma, lam, u, q, partials, capacity):
+        """q = each group (h, v, t) of q + sigma u projected onto the 2-norm ball of radius lam, in place; slots 1, 3."""
+        c = ctypes.c_int(0)
+        rc = self.lib.trk_pdhg_dual_q_iso3(int(N), int(frames), q.numel(), float(sigma), float(lam), u.data_ptr(), q.data_ptr(),
+                                           _ptr(partials), int(capacity), ctypes.byref(c), self.stream())
+        _lib.check(rc, "trk_pdhg_dual_q_iso3")
+        return c.value
+
+    def pdhg_st_dual_iso3(self, handle, sigma, lam, xbar, q, partials, capacity):
+        """pdhg_dual_q_iso3 with u = L xbar formed in registers (a single-rank SpaceTimeDerivative handle)."""
+        c = ctypes.c_int(0)
+        rc = self.lib.trk_pdhg_st_dual_iso3(handle, float(sigma), float(lam), xbar.data_ptr(), q.data_ptr(), _ptr(partials),
+                                            int(capacity), ctypes.byref(c), self.stream())
+        _lib.check(rc, "trk_pdhg_st_dual_iso3")
+        return c.value
+
+    def pdhg_st_primal(self, handle, tau, lo, hi, x, z, q, x_new, xbar, x_true, partials, capacity):
+        """pdhg_primal with v = L^T q gathered in the kernel (a single-rank SpaceTimeDerivative handle)."""
+        c = ctypes.c_int(0)
+        rc = self.lib.trk_pdhg_st_primal(handle, float(tau), float(lo), float(hi), x.data_ptr(), z.data_ptr(), q.data_ptr(),
+                                         x_new.data_ptr(), xbar.data_ptr(), None if x_true is None else x_true.data_ptr(),
+                                         _ptr(partials), int(capacity), ctypes.byref(c), self.stream())
+        _lib.check(rc, "trk_pdhg_st_primal")
+        return c.value
+
+    def pdhg_iterate_iso3(self, hA, hL, N, frames, k_first, n_iters, sigma, tau, lam, lo, hi, fused, b, p, q, w, u, z, v, X, keep, x_prev,
+                          xbar, x_true, NP, np_cap):
+        """pdhg_iterate with the space-time groups of geometry (N, frames)."""
+        rc = self.lib.trk_pdhg_iterate_iso3(hA, hL, int(N), int(frames), int(k_first), int(n_iters), float(sigma), float(tau), float(lam),
+                                            float(lo), float(hi), int(bool(fused)), b.data_ptr(), p.data_ptr(), q.data_ptr(),
+                                            w.data_ptr(), None if u is None else u.data_ptr(), z.data_ptr(),
+                                            None if v is None else v.data_ptr(), X.data_ptr(), X.stride(0), int(bool(keep)),
+                                            x_prev.data_ptr(), xbar.data_ptr(), None if x_true is None else x_true.data_ptr(), _ptr(NP),
+                                            int(np_cap), self.stream())
+        _lib.check(rc, "trk_pdhg_iterate_iso3")
+
     def finalize_batched(self, partials, nblocks, nvals, batches, out, out_stride):
         rc = self.lib.trk_finalize_batched(_ptr(partials), int(nblocks), int(nvals), int(batches), _ptr(out), int(out_stride),
                                            self.stream())

@@ -2,20 +2,25 @@
 and a box in one solve, by the primal-dual hybrid gradient iteration (Chambolle and Pock 2011, algorithm 1, theta = 1; CIL's PDHG).
 With tv='iso' the term is lam sum_g ||(L x)_g||_2, isotropic TV (Rudin, Osher and Fatemi): the horizontal and the vertical difference
 of a pixel form one group, every other row of L a group of its own (include/trk.h: the groups of a geometry (N, frames)).
+With tv='iso3' it is isotropic in space and time, lam sum over voxels of sqrt(h^2 + v^2 + t^2) on the rows of a space-time first
+difference operator: the group of voxel (t, i, j) holds whichever of H_t[i][j], V_t[i][j] and T_t[i][j] exist (CIL's TotalVariation
+on a 2-D + time volume); 'iso' on such an operator is spatially isotropic and temporally l1.
 
 With K = [A; L], duals p and q (zero at the start), x_0 the caller's start projected onto the box and xbar_0 = x_0, per iteration:
     w = A xbar ; p = (p + sigma (w - b)) / (1 + sigma)                      (trk_pdhg_dual_p)
     u = L xbar ; q = clip(q + sigma u, -lam, lam)                           (trk_pdhg_dual_q, or trk_pdhg_tv_dual: u in registers)
                  tv='iso': q = each group of q + sigma u projected onto the 2-norm ball of radius lam
                                                                             (trk_pdhg_dual_q_iso, or trk_pdhg_tv_dual_iso)
+                 tv='iso3': the same with the groups (h, v, t)              (trk_pdhg_dual_q_iso3, or trk_pdhg_st_dual_iso3)
     z = A^T p ; v = L^T q ; x = clip(x - tau (z + v), lower, upper) ; xbar = 2 x - x_previous
-                                                                            (trk_pdhg_primal, or trk_pdhg_tv_primal: v gathered)
+                                                                            (trk_pdhg_primal, or trk_pdhg_tv_primal: v gathered;
+                                                                             tv='iso3' on SpaceTimeDerivative: trk_pdhg_st_primal)
 sigma, tau and lam are host constants, so nothing is read back inside the loop: a whole solve is one enqueue (trk_pdhg_iterate).
 Vectors are fp32, the reported sums fp64 (include/trk.h: the operations and the layout of S).  It converges for
 sigma tau ||K||^2 < 1.
-Not built: three-member groups (h, v, t) for fully isotropic space-time TV (SpaceTimeDerivative is spatially isotropic, temporally
-l1), rectangular images, fused forms for SpaceTimeDerivative / Framelet2D (they run on the generic path), sharded PDHG, diagonal
-preconditioning or adaptive step balancing (`ratio` is the only knob), other data terms.
+Not built: the fused space-time kernels for tv='aniso' / 'iso' (SpaceTimeDerivative runs those two on the generic path), time-sharded
+space-time handles and sharded PDHG, rectangular images and frames, fused forms for Framelet2D, cache hints on the fused kernels'
+loads and stores, diagonal preconditioning or adaptive step balancing (`ratio` is the only knob), other data terms.
 """
 import numpy as np
 
@@ -25,14 +30,14 @@ from ._run import IterationRun
 
 
 def _iso_geometry(L, tv, tv_dims):
-    """None for tv='aniso'; for 'iso' (N, frames) of the isotropic groups on L's rows: the operator's own, or the caller's tv_dims,
-    checked against L.shape."""
+    """None for tv='aniso'; for 'iso' and 'iso3' (N, frames) of the groups on L's rows: the operator's own, or the caller's tv_dims,
+    checked against L.shape ('iso': a tail of further rows may follow the frames' blocks; 'iso3': the space-time rows exactly)."""
     from ..operators import FirstDerivative2D, SpaceTimeDerivative
-    if tv not in ("aniso", "iso"):
-        raise ValueError(f"PDHG: tv must be 'aniso' or 'iso', not {tv!r}")
+    if tv not in ("aniso", "iso", "iso3"):
+        raise ValueError(f"PDHG: tv must be 'aniso', 'iso' or 'iso3', not {tv!r}")
     if tv == "aniso":
         if tv_dims is not None:
-            raise ValueError("PDHG: tv_dims belongs to tv='iso'")
+            raise ValueError("PDHG: tv_dims belongs to tv='iso' and tv='iso3'")
         return None
     if tv_dims is not None:
         try:
@@ -44,11 +49,16 @@ def _iso_geometry(L, tv, tv_dims):
     elif isinstance(L, SpaceTimeDerivative):
         N, frames = L.N, L.nt_global
     else:
-        raise ValueError(f"PDHG: tv='iso' needs tv_dims=(N, frames) for a {type(L).__name__} regulariser: only FirstDerivative2D and "
+        raise ValueError(f"PDHG: tv={tv!r} needs tv_dims=(N, frames) for a {type(L).__name__} regulariser: only FirstDerivative2D and "
                          "SpaceTimeDerivative carry the geometry of their rows")
     if N < 2 or frames < 1:
         raise ValueError("PDHG: tv_dims needs N >= 2 and frames >= 1")
     rows, cols = L.shape
+    if tv == "iso3":
+        if rows != frames * 2 * N * (N - 1) + (frames - 1) * N * N or cols != frames * N * N:
+            raise ValueError(f"PDHG: L is {rows} x {cols}, not the space-time first differences of {frames} images of {N} x {N} "
+                             "(tv='iso3' takes no further rows)")
+        return N, frames
     if rows < frames * 2 * N * (N - 1) or cols != frames * N * N:
         raise ValueError(f"PDHG: L is {rows} x {cols}, not the first differences of {frames} images of {N} x {N} (and a tail of further rows)")
     return N, frames
@@ -62,7 +72,9 @@ class PDHGRun(IterationRun):
     ||x_k - x_{k-1}||^2, ||x_k - x_true||^2, entries of x_k on a bound], the first two at xbar_{k-1} = 2 x_{k-1} - x_{k-2}: the point
     iteration k applies A and L to.  `fused`: None = the fused first-difference kernels where L takes them, True / False forces.
     tv='iso': the isotropic term — sum |L xbar| becomes the sum of the groups' 2-norms; the geometry (N, frames) is
-    FirstDerivative2D's (N, 1), SpaceTimeDerivative's (N, nt) or, for any other operator with that row layout, `tv_dims`."""
+    FirstDerivative2D's (N, 1), SpaceTimeDerivative's (N, nt) or, for any other operator with that row layout, `tv_dims`.
+    tv='iso3': the groups (h, v, t) of a voxel on the space-time row layout; fused=None takes the fused space-time kernels where L is
+    a SpaceTimeDerivative with every frame on this rank whose own geometry it is, every other L the unfused dual behind L.apply."""
 
     def __init__(self, A, b, L, lam, sigma, tau, lower, upper, x0, max_iter, x_true=None, history=True, fused=None, tv="aniso",
                  tv_dims=None):
@@ -86,11 +98,19 @@ class PDHGRun(IterationRun):
         self.geo = _iso_geometry(L, tv, tv_dims)
         super().__init__(A, b, max_iter, x_true, history, "PDHG xHistory")
         eng, max_iter = self.eng, self.max_iter
-        can = bool(hasattr(L, "_h") and hasattr(eng, "pdhg_fused_caps") and eng.pdhg_fused_caps(L._h))
-        if self.geo is not None:                                   # the fused isotropic dual pairs the rows as its handle lays them out
-            can = can and self.geo == (L.N, 1)
-        if fused and not can:
-            raise ValueError("PDHG: fused=True needs a FirstDerivative2D regulariser on the HIP engine")
+        if tv == "iso3":                                           # the fused space-time pair groups the rows as its handle lays them out
+            from ..operators import SpaceTimeDerivative
+            can = bool(isinstance(L, SpaceTimeDerivative) and hasattr(L, "_h") and hasattr(eng, "pdhg_st_dual_iso3")
+                       and not L.sharded and self.geo == (L.N, L.nt_global))
+            if fused and not can:
+                raise ValueError("PDHG: fused=True with tv='iso3' needs a SpaceTimeDerivative regulariser of that geometry, every frame "
+                                 "on one rank, on the HIP engine")
+        else:
+            can = bool(hasattr(L, "_h") and hasattr(eng, "pdhg_fused_caps") and eng.pdhg_fused_caps(L._h))
+            if self.geo is not None:                               # the fused isotropic dual pairs the rows as its handle lays them out
+                can = can and self.geo == (L.N, 1)
+            if fused and not can:
+                raise ValueError("PDHG: fused=True needs a FirstDerivative2D regulariser on the HIP engine")
         self.fused = can if fused is None else bool(fused)
         # the start, projected onto the box in fp32 (the bounds as the kernels round them)
         x0h = np.zeros(n, dtype=np.float32) if x0 is None else _host(x0).astype(np.float32).reshape(-1)
@@ -103,6 +123,8 @@ class PDHGRun(IterationRun):
         self.u, self.v = (None, None) if self.fused else (eng.empty(rows), eng.empty(n))
         if self.geo is None:
             self.cap = eng.pdhg_blocks(m, n, rows, L._h if self.fused else None)
+        elif tv == "iso3":
+            self.cap = eng.pdhg_blocks_iso3(m, n, rows, *self.geo, L._h if self.fused else None)
         else:
             self.cap = eng.pdhg_blocks_iso(m, n, rows, *self.geo, L._h if self.fused else None)
         self.NP = eng.scalars(8 * self.cap * max(1, max_iter))     # zeroed: a kernel writes only its slots of its blocks' rows
@@ -120,14 +142,15 @@ class PDHGRun(IterationRun):
         A.apply(self.xbar, out=self.w)
         eng.pdhg_dual_p(self.sigma, self.w, self.bv, self.p, part, self.cap)
         if self.fused:
-            dual = eng.pdhg_tv_dual if self.geo is None else eng.pdhg_tv_dual_iso
+            dual = {"aniso": eng.pdhg_tv_dual, "iso": eng.pdhg_tv_dual_iso, "iso3": eng.pdhg_st_dual_iso3}[self.tv]
             dual(L._h, self.sigma, self.lam, self.xbar, self.q, part, self.cap)
         else:
             L.apply(self.xbar, out=self.u)
             self._dual_q(self.u, self.q, part)
         A.apply(self.p, out=self.z, transpose=True)
         if self.fused:
-            eng.pdhg_tv_primal(L._h, self.tau, self.lo, self.hi, self.x_cur, self.z, self.q, x_new, self.xbar, self.xt, part, self.cap)
+            primal = eng.pdhg_st_primal if self.tv == "iso3" else eng.pdhg_tv_primal
+            primal(L._h, self.tau, self.lo, self.hi, self.x_cur, self.z, self.q, x_new, self.xbar, self.xt, part, self.cap)
         else:
             L.apply(self.q, out=self.v, transpose=True)
             eng.pdhg_primal(self.tau, self.lo, self.hi, self.x_cur, self.z, self.v, x_new, self.xbar, self.xt, part, self.cap)
@@ -136,14 +159,16 @@ class PDHGRun(IterationRun):
     def _dual_q(self, u, q, part):
         if self.geo is None:
             self.eng.pdhg_dual_q(self.sigma, self.lam, u, q, part, self.cap)
+        elif self.tv == "iso3":
+            self.eng.pdhg_dual_q_iso3(*self.geo, self.sigma, self.lam, u, q, part, self.cap)
         else:
             self.eng.pdhg_dual_q_iso(*self.geo, self.sigma, self.lam, u, q, part, self.cap)
 
     def _c_loop(self):
-        """One library call where A and L both have handles (trk_pdhg_iterate, trk_pdhg_iterate_iso)."""
+        """One library call where A and L both have handles (trk_pdhg_iterate, trk_pdhg_iterate_iso, trk_pdhg_iterate_iso3)."""
         eng = self.eng
-        if not (hasattr(self.A, "_h") and hasattr(self.L, "_h")
-                and hasattr(eng, "pdhg_iterate" if self.geo is None else "pdhg_iterate_iso")):
+        loop = {"aniso": "pdhg_iterate", "iso": "pdhg_iterate_iso", "iso3": "pdhg_iterate_iso3"}[self.tv]
+        if not (hasattr(self.A, "_h") and hasattr(self.L, "_h") and hasattr(eng, loop)):
             return None
 
         def call(k_first, n, X, keep):
@@ -152,7 +177,7 @@ class PDHGRun(IterationRun):
             if self.geo is None:
                 eng.pdhg_iterate(self.A._h, self.L._h, *rest)
             else:
-                eng.pdhg_iterate_iso(self.A._h, self.L._h, *self.geo, *rest)
+                getattr(eng, loop)(self.A._h, self.L._h, *self.geo, *rest)
         return call
 
     def _finish(self):
@@ -177,7 +202,7 @@ class PDHGRun(IterationRun):
         return float(np.sqrt(self.B.host(0, 1)[0]))
 
     def objective_at(self, x):
-        """1/2 ||A x - b||^2 + lam ||L x||_1 (tv='iso': lam sum_g ||(L x)_g||_2) at a device vector x, from one pair of products (the
+        """1/2 ||A x - b||^2 + lam ||L x||_1 (tv='iso', 'iso3': lam sum_g ||(L x)_g||_2) at a device vector x, from one pair of products (the
         sums of the dual kernels on scratch duals; the state of the run is left alone)."""
         eng = self.eng
         w, u = self.A.apply(x), self.L.apply(x)
@@ -200,12 +225,16 @@ def PDHG(A, b, L, lam, max_iter, tol=0, x0=None, x_true=None, lower=0.0, upper=n
     """Primal-dual hybrid gradient: min 1/2 ||A x - b||^2 + lam ||L x||_1 subject to lower <= x <= upper.
 
     A, L: LinearOperators with the same column count (L = Identity: plain l1; FirstDerivative2D: anisotropic TV, on fused kernels);
-    tv: 'aniso' (the l1 norm of L x) or 'iso' — lam sum over pixels of sqrt(h^2 + v^2), isotropic TV: the rows H[i][j] and V[i][j] of
+    tv: 'aniso' (the l1 norm of L x), 'iso' — lam sum over pixels of sqrt(h^2 + v^2), isotropic TV: the rows H[i][j] and V[i][j] of
         the first differences of an image form one group, the last row's H, the last column's V and every further row (the temporal
         rows of SpaceTimeDerivative: spatially isotropic, temporally l1) a group of their own.  The geometry is FirstDerivative2D's
         (fused kernels) and SpaceTimeDerivative's own; tv_dims=(N, frames) gives it for any other operator whose rows are `frames`
         blocks [H ; V] of N x N images and then a tail, such as SparseOp(first_derivative_2d(N, N)).  ValueError where it is missing
         or disagrees with L.shape.  The objectives below then carry the group norms, and info['tv'] = 'iso';
+        'iso3' — lam sum over voxels of sqrt(h^2 + v^2 + t^2), isotropic in space and time: L's rows must be exactly those of
+        SpaceTimeDerivative(N, frames) (its own geometry, on fused kernels; tv_dims for SparseOp(spacetime_derivative(N, N, frames));
+        FirstDerivative2D is (N, 1): 'iso' bit for bit).  The groups are triples, the pairs and singles of the volume's three far
+        faces, and info['tv'] = 'iso3';
     b: (m,) / (m,1); x0: (n,) / (n,1) or None (zeros), projected onto the box; lower / upper: scalars, -inf / +inf allowed.
     Steps: sigma and tau as given; if not both are, sigma tau normK2 = 0.95^2 and sigma / tau = ratio, with normK2 the caller's number
     or else operator_norm_sq([A, L], iters=30, seed=0) — an estimate from below, for which the 0.95 leaves room down to 0.9025 of the
