@@ -1,4 +1,4 @@
-"""PDHG (trips_py_amd/solvers/PDHG.py, csrc/pdhg.hip, the fused forms in csrc/tvops.hip) restated in NumPy, and the seeded problems
+"""PDHG (trips_py_amd/solvers/PDHG.py, csrc/pdhg.hip, the fused forms in csrc/pdhg_tv.hip) restated in NumPy, and the seeded problems
 its tests share (tests/test_pdhg_host.py, tests/test_gpu_pdhg.py).
 
 The restatement takes any (matvec, rmatvec) pair for A and for L and comes in two forms: float64 throughout (`pdhg_f64`), and

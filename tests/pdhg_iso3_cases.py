@@ -1,4 +1,4 @@
-"""PDHG with the isotropic space-time TV term (solvers/PDHG.py tv='iso3', csrc/pdhg.hip, csrc/tvops.hip) restated in NumPy: the
+"""PDHG with the isotropic space-time TV term (solvers/PDHG.py tv='iso3', csrc/pdhg.hip, csrc/pdhg_tv.hip; the operator: csrc/tvops.hip) restated in NumPy: the
 groups (h, v, t) of a geometry (N, frames) on the space-time row layout, the dual in the kernels' operations (include/trk.h: the fp32
 operations of a triple), the space-time differences and their transpose in the kernels' order, and the float64 / storage-faithful
 loops, which return what pdhg_cases.pdhg_f64 returns.  Only the dual update of q and slot 1 of the sums differ from the anisotropic

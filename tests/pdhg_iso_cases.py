@@ -1,4 +1,4 @@
-"""PDHG with the isotropic TV term (solvers/PDHG.py tv='iso', csrc/pdhg.hip, csrc/tvops.hip) restated in NumPy, on the problems of
+"""PDHG with the isotropic TV term (solvers/PDHG.py tv='iso', csrc/pdhg.hip, csrc/pdhg_tv.hip) restated in NumPy, on the problems of
 tests/pdhg_cases.py: the groups of a geometry (N, frames), the isotropic dual in the kernels' operations (include/trk.h: the fp32
 operations of a pair) and the float64 / storage-faithful loops, which return what pdhg_cases.pdhg_f64 returns.  Only the dual update
 of q and slot 1 of the sums differ from the anisotropic restatement; everything else is taken from pdhg_cases."""

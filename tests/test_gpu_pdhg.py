@@ -1,4 +1,4 @@
-"""PDHG on the GPU (csrc/pdhg.hip, the fused forms in csrc/tvops.hip, solvers/PDHG.py) against the NumPy restatement of
+"""PDHG on the GPU (csrc/pdhg.hip, the fused forms in csrc/pdhg_tv.hip, solvers/PDHG.py) against the NumPy restatement of
 tests/pdhg_cases.py: one launch of each kernel on crafted vectors against the storage-faithful form, the fused first-difference
 kernels against the generic path (bit for bit), the one-call C loop against single steps (bit for bit), and whole solves against the
 float64 form."""

@@ -1,4 +1,4 @@
-"""PDHG with isotropic TV on the GPU (k_pdhg_tv_dual<true> and k_pdhg_dual_q_iso in csrc/tvops.hip, the entry points in
+"""PDHG with isotropic TV on the GPU (k_pdhg_tv_dual<kPairs, true> and k_pdhg_tv_dual<kPairs, false> in csrc/pdhg_tv.hip, the entry points in
 csrc/pdhg.hip, solvers/PDHG.py tv='iso') against the NumPy restatement of tests/pdhg_iso_cases.py: one launch of each dual form
 against the storage-faithful form, crafted pairs, the fused form against the unfused one (bit for bit), the one-call C loop against
 single steps (bit for bit), and whole solves against the float64 form."""

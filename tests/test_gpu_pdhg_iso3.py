@@ -1,7 +1,25 @@
-"""PDHG with isotropic space-time TV on the GPU (k_pdhg_st_dual_iso3, k_pdhg_dual_q_iso3 and k_pdhg_st_primal in csrc/tvops.hip, the
-entry points in csrc/pdhg.hip, solvers/PDHG.py tv='iso3') against the NumPy restatement of tests/pdhg_iso3_cases.py: one launch of each
-dual form against the storage-faithful form, crafted groups, the fused pair against the unfused path (bit for bit), the one-call C
-loop against single steps (bit for bit), whole solves against the float64 form, argument checks, and the routing of the older modes."""
+"""PDHG with isotropic space-time TV on the GPU (k_pdhg_tv_dual<kTriples, .> and k_pdhg_tv_primal<., true> in csrc/pdhg_tv.hip, the
+entry points there and in csrc/pdhg.hip, solvers/PDHG.py tv='iso3') against the NumPy restatement of tests/pdhg_iso3_cases.py: one
+launch of each dual form against the storage-faithful form, crafted groups, the fused pair against the unfused path (bit for bit), the
+one-call C loop against single steps (bit for bit), whole solves against the float64 form, argument checks, and the routing of the
+older modes.
+
+The three modes share one dual template k_pdhg_tv_dual<Groups, FUSED> and one primal template k_pdhg_tv_primal<HAS_XT, TEMPORAL>.
+Which test of this file reaches which instantiation (the kRows dual and the rest of the 2-D ones: test_gpu_pdhg.py, test_gpu_pdhg_iso.py):
+
+  entry point                               kernel<template arguments>             covering test
+  trk_pdhg_st_dual_iso3                     k_pdhg_tv_dual<kTriples, true>         fused_dual_against_the_restatement, crafted_*, fused_equals_unfused,
+                                                                                   one_frame_is_the_2d_fused_pair, run_equals_steps, solve_against_float64
+  trk_pdhg_dual_q_iso3                      k_pdhg_tv_dual<kTriples, false>        unfused_dual_against_the_restatement, one_frame_is_the_isotropic_dual,
+                                                                                   crafted_*, fused_equals_unfused, run_equals_steps (fused=False, csr)
+  trk_pdhg_dual_q_iso                       k_pdhg_tv_dual<kPairs, false>          one_frame_is_the_isotropic_dual, fused_equals_unfused (frames in z),
+                                                                                   old_routing_is_unchanged
+  trk_pdhg_tv_dual_iso                      k_pdhg_tv_dual<kPairs, true>           one_frame_is_the_2d_fused_pair, old_routing_is_unchanged
+  trk_pdhg_st_primal, x_true                k_pdhg_tv_primal<true, true>           fused_equals_unfused[True], one_frame_is_the_2d_fused_pair,
+                                                                                   run_equals_steps, solve_against_float64
+  trk_pdhg_st_primal, no x_true             k_pdhg_tv_primal<false, true>          fused_equals_unfused[False], one_frame_is_the_2d_fused_pair
+  trk_pdhg_tv_primal, x_true / none         k_pdhg_tv_primal<true / false, false>  one_frame_is_the_2d_fused_pair, old_routing_is_unchanged (none)
+  the argument checks of all of them        (no kernel)                            argument_checks_come_first"""
 import numpy as np
 import pytest
 import torch
@@ -154,6 +172,31 @@ def test_one_frame_is_the_isotropic_dual(eng, N):
     assert torch.equal(q3, q2) and not torch.equal(q3, eng.to_vec(q0))
     c3, c2 = NP3.host().reshape(CAP, 8).sum(axis=0), NP2.host().reshape(CAP, 8).sum(axis=0)
     _sums_match(c3[[1, 3]], c2[[1, 3]], N)
+
+
+@pytest.mark.parametrize("N", [2, 5, 33, 260])
+def test_one_frame_is_the_2d_fused_pair(eng, N):
+    """frames = 1: the space-time handle's fused pair leaves the bits of the 2-D handle's fused pair on the same operands — the
+    kTriples dual with no temporal member against the kPairs dual, the TEMPORAL primal with both neighbours NULL against the
+    plain one.  At one frame grid3 is grid2, so every block's row of partials is compared as it stands.  2: the smallest; 5: an odd
+    batch tail; 33: short of a 64-lane wave by half; 260: a second column block."""
+    from trips_py_amd.operators import FirstDerivative2D, SpaceTimeDerivative
+    L3, L2 = SpaceTimeDerivative(N, 1, engine=eng), FirstDerivative2D(N, engine=eng)
+    d = {k: eng.to_vec(a) for k, a in _st_inputs(N, 1).items()}
+    q3, q2, NP3, NP2 = d["q"].clone(), d["q"].clone(), eng.scalars(8 * CAP), eng.scalars(8 * CAP)
+    nb = eng.pdhg_st_dual_iso3(L3._h, SIGMA, LAM, d["xbar"], q3, NP3.ref(0), CAP)
+    assert nb == eng.pdhg_tv_dual_iso(L2._h, SIGMA, LAM, d["xbar"], q2, NP2.ref(0), CAP) == _grid3(N, 1)
+    assert torch.equal(q3, q2) and not torch.equal(q3, d["q"])
+    p3, p2 = NP3.host().reshape(CAP, 8), NP2.host().reshape(CAP, 8)
+    assert np.array_equal(p3[:, [1, 3]], p2[:, [1, 3]]) and p3[:nb, 1].all()
+    for xt in (d["xt"], None):
+        x3, b3, x2, b2 = (torch.empty_like(d["x"]) for _ in range(4))
+        NP3, NP2 = eng.scalars(8 * CAP), eng.scalars(8 * CAP)
+        assert eng.pdhg_st_primal(L3._h, TAU, LO, HI, d["x"], d["z"], q3, x3, b3, xt, NP3.ref(0), CAP) == nb
+        assert eng.pdhg_tv_primal(L2._h, TAU, LO, HI, d["x"], d["z"], q2, x2, b2, xt, NP2.ref(0), CAP) == nb
+        assert torch.equal(x3, x2) and torch.equal(b3, b2) and not torch.equal(x3, d["x"])
+        p3, p2 = NP3.host().reshape(CAP, 8), NP2.host().reshape(CAP, 8)
+        assert np.array_equal(p3[:, 4:], p2[:, 4:]) and p3[:nb, 4].all() and (xt is None) == (not p3[:, 6].any())
 
 
 # ====================================================================== (3) crafted groups through both dual forms

@@ -9,7 +9,8 @@ calls; outputs start as NaN, so a store that was skipped shows.  Time-sharded ha
 (trk_spacetime_create(N, nt_local, has_next, has_prev)) and fed their halos by hand from the global vector (trk_tv_halo,
 trk_spacetime_set_halo): their outputs must be the bits of the one-handle result.
 
-Which test reaches which instantiation launched from tvops.hip's first-difference entry points:
+Which test reaches which instantiation launched from tvops.hip's first-difference entry points (k_d2_adj gathers through
+AdjGather<TEMPORAL> of tv_internal.h, which PDHG's fused primal in pdhg_tv.hip shares: tests/test_gpu_pdhg_iso3.py has that table):
 
   entry point                               kernel<template arguments>             covering test
   trk_op_apply, 2-D, forward                k_d2_fwd<false>                        apply_2d, apply_batched
@@ -379,7 +380,7 @@ def test_capped_grid_tv_grad(eng, nt, kind, combos, forms):
 @pytest.mark.parametrize("N", [5, 257])
 def test_sharded(eng, Wn, ntl, N):
     """W slices of nt_local frames, each on a handle of its own fed by hand: every output mapped into the global layout is the
-    one-handle result bit for bit — the recomputed previous-boundary weight row included (tvops.hip:180) — and within bound of
+    one-handle result bit for bit — the recomputed previous-boundary weight row included (tvops.hip:134) — and within bound of
     float64; the slices' partial sums add up to the global ones."""
     nt = Wn * ntl
     npix = N * N

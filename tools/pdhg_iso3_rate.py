@@ -80,10 +80,10 @@ def measure(N, frames, angles, steps, warmup):
     NP = eng.scalars(8 * cap)
     X0, X1 = run.X[0], run.X[1]
     kernels = {
-        "k_pdhg_st_dual_iso3": (4 * n + 8 * rows, lambda: eng.pdhg_st_dual_iso3(L._h, sigma, lam, run.xbar, run.q, NP.ref(0), cap)),
-        "k_pdhg_st_primal": (16 * n + 4 * rows, lambda: eng.pdhg_st_primal(L._h, tau, 0.0, np.inf, X0, run.z, run.q, X1, run.xbar, None,
+        "k_pdhg_tv_dual<kTriples, true>": (4 * n + 8 * rows, lambda: eng.pdhg_st_dual_iso3(L._h, sigma, lam, run.xbar, run.q, NP.ref(0), cap)),
+        "k_pdhg_tv_primal<false, true>": (16 * n + 4 * rows, lambda: eng.pdhg_st_primal(L._h, tau, 0.0, np.inf, X0, run.z, run.q, X1, run.xbar, None,
                                                                         NP.ref(0), cap)),
-        "k_pdhg_dual_q_iso3": (12 * rows, lambda: eng.pdhg_dual_q_iso3(N, frames, sigma, lam, run.u, run.q, NP.ref(0), cap)),
+        "k_pdhg_tv_dual<kTriples, false>": (12 * rows, lambda: eng.pdhg_dual_q_iso3(N, frames, sigma, lam, run.u, run.q, NP.ref(0), cap)),
         "L_apply (k_d2_fwd + k_time_fwd)": (12 * n + 4 * rows, lambda: L.apply(run.xbar, out=run.u)),
         "L_apply_transpose (k_d2_adj)": (4 * rows + 4 * n, lambda: L.apply(run.q, out=run.v, transpose=True)),
         "k_pdhg_primal": (20 * n, lambda: eng.pdhg_primal(tau, 0.0, np.inf, X0, run.z, run.v, X1, run.xbar, None, NP.ref(0), cap)),

@@ -80,13 +80,13 @@ def measure(N, steps, warmup, tv="aniso"):
         "k_pdhg_dual_p": (16 * n, lambda: eng.pdhg_dual_p(sigma, run.w, run.bv, run.p, NP.ref(0), cap)),
         "k_pdhg_dual_q": (12 * rows, lambda: eng.pdhg_dual_q(sigma, lam, run.u, run.q, NP.ref(0), cap)),
         "k_pdhg_primal": (20 * n, lambda: eng.pdhg_primal(tau, 0.0, np.inf, X0, run.z, run.v, X1, run.xbar, None, NP.ref(0), cap)),
-        "k_pdhg_tv_dual": (4 * n + 8 * rows, lambda: eng.pdhg_tv_dual(L._h, sigma, lam, run.xbar, run.q, NP.ref(0), cap)),
-        "k_pdhg_tv_primal": (16 * n + 4 * rows, lambda: eng.pdhg_tv_primal(L._h, tau, 0.0, np.inf, X0, run.z, run.q, X1, run.xbar, None,
+        "k_pdhg_tv_dual<kRows, true>": (4 * n + 8 * rows, lambda: eng.pdhg_tv_dual(L._h, sigma, lam, run.xbar, run.q, NP.ref(0), cap)),
+        "k_pdhg_tv_primal<false, false>": (16 * n + 4 * rows, lambda: eng.pdhg_tv_primal(L._h, tau, 0.0, np.inf, X0, run.z, run.q, X1, run.xbar, None,
                                                                         NP.ref(0), cap)),
     }
     if tv == "iso":
-        kernels["k_pdhg_tv_dual_iso"] = (4 * n + 8 * rows, lambda: eng.pdhg_tv_dual_iso(L._h, sigma, lam, run.xbar, run.q, NP.ref(0), cap))
-        kernels["k_pdhg_dual_q_iso"] = (12 * rows, lambda: eng.pdhg_dual_q_iso(N, 1, sigma, lam, run.u, run.q, NP.ref(0), cap))
+        kernels["k_pdhg_tv_dual<kPairs, true>"] = (4 * n + 8 * rows, lambda: eng.pdhg_tv_dual_iso(L._h, sigma, lam, run.xbar, run.q, NP.ref(0), cap))
+        kernels["k_pdhg_tv_dual<kPairs, false>"] = (12 * rows, lambda: eng.pdhg_dual_q_iso(N, 1, sigma, lam, run.u, run.q, NP.ref(0), cap))
     for name, (nbytes, call) in kernels.items():
         def many():
             for _ in range(steps):

@@ -6,12 +6,13 @@
 //   z = A^T p' ;  v = L^T q' ;  x' = clip(x - tau (z + v), lo, hi) ;  xbar' = 2 x' - x
 // Isotropic TV (the *_iso entry points): lam sum_g ||(L x)_g||_2 with the groups of a geometry (N, frames) on the first-difference
 // row layout (include/trk.h); q' = every group of q + sig u projected onto the 2-norm ball of radius lam, everything else unchanged.
-// The grouped rows run on k_pdhg_dual_q_iso (tvops.hip: the column-thread layout), the tail rows on k_pdhg_dual_q below.
+// The grouped rows run on k_pdhg_tv_dual<kPairs, false> (pdhg_tv.hip: the column-thread layout), the tail rows on k_pdhg_dual_q below.
 // Isotropic space-time TV (the *_iso3 entry points): the groups (h, v, t) of a voxel on the space-time row layout, one kernel
-// (k_pdhg_dual_q_iso3) or, on the space-time handle, the fused pair k_pdhg_st_dual_iso3 / k_pdhg_st_primal of tvops.hip.
+// (k_pdhg_tv_dual<kTriples, false>) or, on the space-time handle, the fused pair k_pdhg_tv_dual<kTriples, true> /
+// k_pdhg_tv_primal<., true> of pdhg_tv.hip.
 // sig, tau, lam, lo, hi are host constants: nothing is read back inside the loop and trk_pdhg_iterate enqueues a whole solve.
-// The three streaming kernels are here; the fused forms for the 2-D first differences (no vector of the length of L xbar or L^T q
-// in memory) are in tvops.hip and share one entry (pdhg_internal.h).  Vectors fp32, sums fp64 block partials, no atomics: every
+// The three streaming kernels are here; the fused forms for the first differences (no vector of the length of L xbar or L^T q
+// in memory) are in pdhg_tv.hip and share one entry (pdhg_internal.h).  Vectors fp32, sums fp64 block partials, no atomics: every
 // result is reproducible from run to run.  docs/kernels/pdhg.md: the byte count, why xbar is stored.
 #include "vec_internal.h"
 #include "pdhg_internal.h"
@@ -125,15 +126,74 @@ __global__ __launch_bounds__(NT) void k_pdhg_primal(int64_t n, float tau, float 
 
 inline bool finite_pos(double v) { return v > 0.0 && v < __builtin_inf(); }
 
-// the rows [H ; V] of `frames` N x N images: where the tail of an isotropic L begins
-inline int64_t iso_grouped_rows(int N, int frames) { return (int64_t)frames * 2 * N * (N - 1); }
+// the C entries of a mode, by Groups (pdhg_internal.h): their names open the error texts
+const char* const kBlocksEntry[] = {"trk_pdhg_blocks", "trk_pdhg_blocks_iso", "trk_pdhg_blocks_iso3"};
+const char* const kDualQEntry[] = {"trk_pdhg_dual_q", "trk_pdhg_dual_q_iso", "trk_pdhg_dual_q_iso3"};
 
-// the rows of the space-time operator of `frames` N x N images: the grouped rows, then the (frames - 1) N^2 temporal rows
-inline int64_t iso3_rows(int N, int frames) { return iso_grouped_rows(N, frames) + (int64_t)(frames - 1) * N * N; }
+// the rows of L that the groups g of geometry (N, frames) cover: the rows [H ; V] of `frames` N x N images (kPairs: a tail of groups
+// of one may follow) and, with kTriples, the (frames - 1) N^2 temporal rows of the space-time operator
+inline int64_t grouped_rows(Groups g, int N, int frames) {
+  return (int64_t)frames * 2 * N * (N - 1) + (g == Groups::kTriples ? (int64_t)(frames - 1) * N * N : 0);
+}
 
-// How the rows of L are grouped in the dual update of q: every row alone (the l1 term), the pairs (h, v) of a pixel, or the
-// groups (h, v, t) of a voxel.
-enum class Groups { kRows, kIso, kIso3 };
+// what the block counts and the unfused grouped duals ask of a geometry and of the rows of L
+int check_geometry(const char* who, Groups g, int N, int frames, int64_t rows) {
+  TRK_REQUIRE(N >= 2 && frames >= 1 && frames <= 65535, "%s: need N >= 2, 1 <= frames <= 65535", who);
+  const int64_t want = grouped_rows(g, N, frames);
+  if (g == Groups::kTriples)
+    TRK_REQUIRE(rows == want, "%s: %lld rows are not the %lld of the space-time differences of %d images of %d x %d", who,
+                (long long)rows, (long long)want, frames, N, N);
+  else
+    TRK_REQUIRE(rows >= want, "%s: %lld rows are fewer than the %lld of %d images of %d x %d", who, (long long)rows, (long long)want,
+                frames, N, N);
+  return TRK_OK;
+}
+
+// The largest block count of an iteration's kernels, behind trk_pdhg_blocks, trk_pdhg_blocks_iso and trk_pdhg_blocks_iso3.
+int pdhg_blocks(Groups g, int64_t m, int64_t n, int64_t rows, int N, int frames, const trk_op* L_fused, int* blocks) {
+  const char* who = kBlocksEntry[(int)g];
+  TRK_REQUIRE(blocks && m >= 1 && n >= 1 && rows >= 1, "%s: need m, n, rows >= 1", who);
+  int64_t longest = m > n ? m : n;                       // of the vectors the streaming kernels sweep
+  if (g == Groups::kRows) longest = rows > longest ? rows : longest;
+  else if (int rc = check_geometry(who, g, N, frames, rows)) return rc;
+  int t = 0;                                             // the column-thread kernels' blocks
+  if (L_fused) {
+    int hN = 0, hf = 0;
+    if (!pdhg_fusable(L_fused, g, &hN, &hf)) return fail(TRK_EUNSUPPORTED, "%s: %s", who, pdhg_fusable_wanted(g));
+    if (g == Groups::kTriples)
+      TRK_REQUIRE(hN == N && hf == frames, "%s: the fused forms take the geometry of their handle, (%d, %d)", who, hN, hf);
+    t = pdhg_tv_blocks(g, hN, hf);
+  } else if (g != Groups::kRows) {                       // grouped rows, then the tail's
+    const int64_t off = grouped_rows(g, N, frames);
+    t = pdhg_tv_blocks(g, N, frames) + (rows > off ? stream_grid(rows - off) : 0);
+  }
+  const int sg = stream_grid(longest);
+  *blocks = t > sg ? t : sg;
+  return TRK_OK;
+}
+
+// The unfused grouped duals behind trk_pdhg_dual_q_iso and trk_pdhg_dual_q_iso3: the column-thread kernel on the grouped rows, then
+// (kPairs) the streaming kernel on a tail of groups of one.
+int grouped_dual_q(Groups g, int N, int frames, int64_t rows, double sigma, double lam, const float* u, float* q, double* partials,
+                   int capacity_blocks, int* n_blocks, trk_stream st) {
+  const char* who = kDualQEntry[(int)g];
+  TRK_REQUIRE(u && q && partials && n_blocks, "%s: NULL argument", who);
+  if (int rc = check_geometry(who, g, N, frames, rows)) return rc;
+  TRK_REQUIRE(finite_pos(sigma), "%s: sigma must be finite and > 0", who);
+  TRK_REQUIRE(lam >= 0.0 && lam < __builtin_inf(), "%s: lam must be finite and >= 0", who);
+  TRK_REQUIRE(q != u, "%s: q must not alias u", who);
+  const int64_t off = grouped_rows(g, N, frames);
+  const int grouped = pdhg_tv_blocks(g, N, frames), tail = rows > off ? stream_grid(rows - off) : 0;
+  TRK_REQUIRE(grouped + tail <= capacity_blocks, "%s: partial buffer too small (%d blocks needed)", who, grouped + tail);
+  *n_blocks = grouped + tail;
+  pdhg_grouped_dual_launch(g, N, frames, (float)sigma, (float)lam, u, q, partials, (hipStream_t)st);
+  TRK_LAUNCH_CHECK();
+  if (tail) {   // groups of one: the streaming kernel on the slices, its blocks' rows of partials behind the grouped kernel's
+    int nt = 0;
+    return trk_pdhg_dual_q(rows - off, sigma, lam, u + off, q + off, partials + 8 * (int64_t)grouped, capacity_blocks - grouped, &nt, st);
+  }
+  return TRK_OK;
+}
 
 // The loop of trk_pdhg_iterate, trk_pdhg_iterate_iso and trk_pdhg_iterate_iso3 (the groups of geometry (N, frames)).  Only the
 // dual update of q differs, and with `fused` the handle the two fused kernels belong to.
@@ -141,28 +201,24 @@ int pdhg_iterate(const char* who, trk_op* A, trk_op* L, Groups groups, int N, in
                  double tau, double lam, double lo, double hi, int fused, const float* b, float* p, float* q, float* w, float* u, float* z,
                  float* v, float* X, int64_t x_ld, int keep_history, const float* x_prev, float* xbar, const float* x_true, double* NP,
                  int np_capacity_blocks, trk_stream stream) {
-  const bool iso = groups == Groups::kIso, iso3 = groups == Groups::kIso3;
   TRK_REQUIRE(A && L && b && p && q && w && z && X && x_prev && xbar && NP, "%s: NULL argument", who);
   TRK_REQUIRE(fused || (u && v), "%s: the generic path needs u and v", who);
   TRK_REQUIRE(k_first >= 1 && n_iters >= 0, "%s: need k_first >= 1, n_iters >= 0", who);
   TRK_REQUIRE(L->cols == A->cols, "%s: A and L must have the same number of columns", who);
   const int64_t m = A->rows, n = A->cols, rows = L->rows;
-  int need = 0;
-  if (iso3) {
-    TRK_REQUIRE(rows == iso3_rows(N, frames) && n == (int64_t)frames * N * N,
+  int need = 0, hN = 0, hf = 0;
+  if (groups == Groups::kTriples)
+    TRK_REQUIRE(rows == grouped_rows(groups, N, frames) && n == (int64_t)frames * N * N,
                 "%s: L is %lld x %lld, not the space-time first differences of %d images of %d x %d", who, (long long)rows, (long long)n,
                 frames, N, N);
-    if (int rc = trk_pdhg_blocks_iso3(m, n, rows, N, frames, fused ? L : nullptr, &need)) return rc;  // TRK_EUNSUPPORTED: no fused form
-  } else if (iso) {
-    TRK_REQUIRE(rows >= iso_grouped_rows(N, frames) && n == (int64_t)frames * N * N,
+  else if (groups == Groups::kPairs)
+    TRK_REQUIRE(rows >= grouped_rows(groups, N, frames) && n == (int64_t)frames * N * N,
                 "%s: L is %lld x %lld, not the first differences of %d images of %d x %d (and a tail)", who, (long long)rows,
                 (long long)n, frames, N, N);
-    if (int rc = trk_pdhg_blocks_iso(m, n, rows, N, frames, fused ? L : nullptr, &need)) return rc;   // TRK_EUNSUPPORTED: no fused form
-    TRK_REQUIRE(!fused || (pdhg_tv_size(L) == N && frames == 1), "%s: the fused form takes the geometry of its handle, (%d, 1)", who,
-                pdhg_tv_size(L));
-  } else {
-    if (int rc = trk_pdhg_blocks(m, n, rows, fused ? L : nullptr, &need)) return rc;
-  }
+  if (int rc = pdhg_blocks(groups, m, n, rows, N, frames, fused ? L : nullptr, &need)) return rc;      // TRK_EUNSUPPORTED: no fused form
+  if (groups == Groups::kPairs && fused)
+    TRK_REQUIRE(pdhg_fusable(L, groups, &hN, &hf) && hN == N && frames == 1, "%s: the fused form takes the geometry of its handle, (%d, 1)",
+                who, hN);
   TRK_REQUIRE(need <= np_capacity_blocks, "%s: partial buffer too small (%d blocks needed)", who, need);
   for (int k = k_first; k < k_first + n_iters; ++k) {
     double* part = NP + 8 * (int64_t)np_capacity_blocks * (k - 1);
@@ -171,20 +227,16 @@ int pdhg_iterate(const char* who, trk_op* A, trk_op* L, Groups groups, int N, in
     if ((rc = trk_op_apply(A, 0, xbar, 0, w, 0, 1, nullptr, stream))) return rc;                       // w = A xbar
     if ((rc = trk_pdhg_dual_p(m, sigma, w, b, p, part, np_capacity_blocks, &nb, stream))) return rc;
     if (fused) {
-      rc = iso3  ? trk_pdhg_st_dual_iso3(L, sigma, lam, xbar, q, part, np_capacity_blocks, &nb, stream)
-           : iso ? trk_pdhg_tv_dual_iso(L, sigma, lam, xbar, q, part, np_capacity_blocks, &nb, stream)
-                 : trk_pdhg_tv_dual(L, sigma, lam, xbar, q, part, np_capacity_blocks, &nb, stream);
+      rc = pdhg_fused_dual(groups, L, sigma, lam, xbar, q, part, np_capacity_blocks, &nb, stream);
     } else {
       if ((rc = trk_op_apply(L, 0, xbar, 0, u, 0, 1, nullptr, stream))) return rc;                     // u = L xbar
-      rc = iso3  ? trk_pdhg_dual_q_iso3(N, frames, rows, sigma, lam, u, q, part, np_capacity_blocks, &nb, stream)
-           : iso ? trk_pdhg_dual_q_iso(N, frames, rows, sigma, lam, u, q, part, np_capacity_blocks, &nb, stream)
-                 : trk_pdhg_dual_q(rows, sigma, lam, u, q, part, np_capacity_blocks, &nb, stream);
+      rc = groups == Groups::kRows ? trk_pdhg_dual_q(rows, sigma, lam, u, q, part, np_capacity_blocks, &nb, stream)
+                                   : grouped_dual_q(groups, N, frames, rows, sigma, lam, u, q, part, np_capacity_blocks, &nb, stream);
     }
     if (rc) return rc;
     if ((rc = trk_op_apply(A, 1, p, 0, z, 0, 1, nullptr, stream))) return rc;                          // z = A^T p'
     if (fused) {
-      rc = iso3 ? trk_pdhg_st_primal(L, tau, lo, hi, x_prev, z, q, x_new, xbar, x_true, part, np_capacity_blocks, &nb, stream)
-                : trk_pdhg_tv_primal(L, tau, lo, hi, x_prev, z, q, x_new, xbar, x_true, part, np_capacity_blocks, &nb, stream);
+      rc = pdhg_fused_primal(groups, L, tau, lo, hi, x_prev, z, q, x_new, xbar, x_true, part, np_capacity_blocks, &nb, stream);
     } else {
       if ((rc = trk_op_apply(L, 1, q, 0, v, 0, 1, nullptr, stream))) return rc;                        // v = L^T q'
       rc = trk_pdhg_primal(n, tau, lo, hi, x_prev, z, v, x_new, xbar, x_true, part, np_capacity_blocks, &nb, stream);
@@ -201,15 +253,7 @@ int pdhg_iterate(const char* who, trk_op* A, trk_op* L, Groups groups, int N, in
 extern "C" {
 
 int trk_pdhg_blocks(int64_t m, int64_t n, int64_t rows, const trk_op* L_fused, int* blocks) {
-  TRK_REQUIRE(blocks && m >= 1 && n >= 1 && rows >= 1, "trk_pdhg_blocks: need m, n, rows >= 1");
-  int g = stream_grid(m > n ? (m > rows ? m : rows) : (n > rows ? n : rows));
-  if (L_fused) {
-    const int t = pdhg_tv_blocks(L_fused);
-    if (t == 0) return fail(TRK_EUNSUPPORTED, "trk_pdhg_blocks: the fused forms take a handle from trk_deriv2d_create only");
-    if (t > g) g = t;
-  }
-  *blocks = g;
-  return TRK_OK;
+  return pdhg_blocks(Groups::kRows, m, n, rows, 0, 0, L_fused, blocks);
 }
 
 int trk_pdhg_dual_p(int64_t m, double sigma, const float* w, const float* b, float* p, double* partials, int capacity_blocks,
@@ -247,42 +291,12 @@ int trk_pdhg_dual_q(int64_t rows, double sigma, double lam, const float* u, floa
 }
 
 int trk_pdhg_blocks_iso(int64_t m, int64_t n, int64_t rows, int N, int frames, const trk_op* L_fused, int* blocks) {
-  TRK_REQUIRE(blocks && m >= 1 && n >= 1 && rows >= 1, "trk_pdhg_blocks_iso: need m, n, rows >= 1");
-  TRK_REQUIRE(N >= 2 && frames >= 1 && frames <= 65535, "trk_pdhg_blocks_iso: need N >= 2, 1 <= frames <= 65535");
-  const int64_t off = iso_grouped_rows(N, frames);
-  TRK_REQUIRE(rows >= off, "trk_pdhg_blocks_iso: %lld rows are fewer than the %lld of %d images of %d x %d", (long long)rows,
-              (long long)off, frames, N, N);
-  int g = stream_grid(m > n ? m : n), t;
-  if (L_fused) {
-    t = pdhg_tv_blocks(L_fused);
-    if (t == 0) return fail(TRK_EUNSUPPORTED, "trk_pdhg_blocks_iso: the fused forms take a handle from trk_deriv2d_create only");
-  } else {
-    t = pdhg_iso_blocks(N, frames) + (rows > off ? stream_grid(rows - off) : 0);      // grouped rows, then the tail's
-  }
-  *blocks = t > g ? t : g;
-  return TRK_OK;
+  return pdhg_blocks(Groups::kPairs, m, n, rows, N, frames, L_fused, blocks);
 }
 
 int trk_pdhg_dual_q_iso(int N, int frames, int64_t rows, double sigma, double lam, const float* u, float* q, double* partials,
                         int capacity_blocks, int* n_blocks, trk_stream st) {
-  TRK_REQUIRE(u && q && partials && n_blocks, "trk_pdhg_dual_q_iso: NULL argument");
-  TRK_REQUIRE(N >= 2 && frames >= 1 && frames <= 65535, "trk_pdhg_dual_q_iso: need N >= 2, 1 <= frames <= 65535");
-  const int64_t off = iso_grouped_rows(N, frames);
-  TRK_REQUIRE(rows >= off, "trk_pdhg_dual_q_iso: %lld rows are fewer than the %lld of %d images of %d x %d", (long long)rows,
-              (long long)off, frames, N, N);
-  TRK_REQUIRE(finite_pos(sigma), "trk_pdhg_dual_q_iso: sigma must be finite and > 0");
-  TRK_REQUIRE(lam >= 0.0 && lam < __builtin_inf(), "trk_pdhg_dual_q_iso: lam must be finite and >= 0");
-  TRK_REQUIRE(q != u, "trk_pdhg_dual_q_iso: q must not alias u");
-  const int grouped = pdhg_iso_blocks(N, frames), tail = rows > off ? stream_grid(rows - off) : 0;
-  TRK_REQUIRE(grouped + tail <= capacity_blocks, "trk_pdhg_dual_q_iso: partial buffer too small (%d blocks needed)", grouped + tail);
-  *n_blocks = grouped + tail;
-  pdhg_dual_q_iso_launch(N, frames, (float)sigma, (float)lam, u, q, partials, (hipStream_t)st);
-  TRK_LAUNCH_CHECK();
-  if (tail) {   // groups of one: the streaming kernel on the slices, its blocks' rows of partials behind the grouped kernel's
-    int nt = 0;
-    return trk_pdhg_dual_q(rows - off, sigma, lam, u + off, q + off, partials + 8 * (int64_t)grouped, capacity_blocks - grouped, &nt, st);
-  }
-  return TRK_OK;
+  return grouped_dual_q(Groups::kPairs, N, frames, rows, sigma, lam, u, q, partials, capacity_blocks, n_blocks, st);
 }
 
 int trk_pdhg_primal(int64_t n, double tau, double lo, double hi, const float* x, const float* z, const float* v, float* x_new,
@@ -320,44 +334,17 @@ int trk_pdhg_iterate_iso(trk_op* A, trk_op* L, int N, int frames, int k_first, i
                          float* X, int64_t x_ld, int keep_history, const float* x_prev, float* xbar, const float* x_true, double* NP,
                          int np_capacity_blocks, trk_stream stream) {
   TRK_REQUIRE(N >= 2 && frames >= 1, "trk_pdhg_iterate_iso: need N >= 2, frames >= 1");
-  return pdhg_iterate("trk_pdhg_iterate_iso", A, L, Groups::kIso, N, frames, k_first, n_iters, sigma, tau, lam, lo, hi, fused, b, p, q, w, u, z,
+  return pdhg_iterate("trk_pdhg_iterate_iso", A, L, Groups::kPairs, N, frames, k_first, n_iters, sigma, tau, lam, lo, hi, fused, b, p, q, w, u, z,
                       v, X, x_ld, keep_history, x_prev, xbar, x_true, NP, np_capacity_blocks, stream);
 }
 
 int trk_pdhg_blocks_iso3(int64_t m, int64_t n, int64_t rows, int N, int frames, const trk_op* L_fused, int* blocks) {
-  TRK_REQUIRE(blocks && m >= 1 && n >= 1 && rows >= 1, "trk_pdhg_blocks_iso3: need m, n, rows >= 1");
-  TRK_REQUIRE(N >= 2 && frames >= 1 && frames <= 65535, "trk_pdhg_blocks_iso3: need N >= 2, 1 <= frames <= 65535");
-  TRK_REQUIRE(rows == iso3_rows(N, frames),
-              "trk_pdhg_blocks_iso3: %lld rows are not the %lld of the space-time differences of %d images of %d x %d", (long long)rows,
-              (long long)iso3_rows(N, frames), frames, N, N);
-  if (L_fused) {
-    int hN = 0, hf = 0;
-    if (!pdhg_st_geometry(L_fused, &hN, &hf))
-      return fail(TRK_EUNSUPPORTED,
-                  "trk_pdhg_blocks_iso3: the fused space-time forms take a handle from trk_spacetime_create with every frame on one rank");
-    TRK_REQUIRE(hN == N && hf == frames, "trk_pdhg_blocks_iso3: the fused forms take the geometry of their handle, (%d, %d)", hN, hf);
-  }
-  const int g = stream_grid(m > n ? m : n), t = pdhg_iso3_blocks(N, frames);   // the fused and the unfused dual share one grid
-  *blocks = t > g ? t : g;
-  return TRK_OK;
+  return pdhg_blocks(Groups::kTriples, m, n, rows, N, frames, L_fused, blocks);
 }
 
 int trk_pdhg_dual_q_iso3(int N, int frames, int64_t rows, double sigma, double lam, const float* u, float* q, double* partials,
                          int capacity_blocks, int* n_blocks, trk_stream st) {
-  TRK_REQUIRE(u && q && partials && n_blocks, "trk_pdhg_dual_q_iso3: NULL argument");
-  TRK_REQUIRE(N >= 2 && frames >= 1 && frames <= 65535, "trk_pdhg_dual_q_iso3: need N >= 2, 1 <= frames <= 65535");
-  TRK_REQUIRE(rows == iso3_rows(N, frames),
-              "trk_pdhg_dual_q_iso3: %lld rows are not the %lld of the space-time differences of %d images of %d x %d", (long long)rows,
-              (long long)iso3_rows(N, frames), frames, N, N);
-  TRK_REQUIRE(finite_pos(sigma), "trk_pdhg_dual_q_iso3: sigma must be finite and > 0");
-  TRK_REQUIRE(lam >= 0.0 && lam < __builtin_inf(), "trk_pdhg_dual_q_iso3: lam must be finite and >= 0");
-  TRK_REQUIRE(q != u, "trk_pdhg_dual_q_iso3: q must not alias u");
-  const int nb = pdhg_iso3_blocks(N, frames);
-  TRK_REQUIRE(nb <= capacity_blocks, "trk_pdhg_dual_q_iso3: partial buffer too small (%d blocks needed)", nb);
-  *n_blocks = nb;
-  pdhg_dual_q_iso3_launch(N, frames, (float)sigma, (float)lam, u, q, partials, (hipStream_t)st);
-  TRK_LAUNCH_CHECK();
-  return TRK_OK;
+  return grouped_dual_q(Groups::kTriples, N, frames, rows, sigma, lam, u, q, partials, capacity_blocks, n_blocks, st);
 }
 
 int trk_pdhg_iterate_iso3(trk_op* A, trk_op* L, int N, int frames, int k_first, int n_iters, double sigma, double tau, double lam,
@@ -365,7 +352,7 @@ int trk_pdhg_iterate_iso3(trk_op* A, trk_op* L, int N, int frames, int k_first, 
                           float* X, int64_t x_ld, int keep_history, const float* x_prev, float* xbar, const float* x_true, double* NP,
                           int np_capacity_blocks, trk_stream stream) {
   TRK_REQUIRE(N >= 2 && frames >= 1, "trk_pdhg_iterate_iso3: need N >= 2, frames >= 1");
-  return pdhg_iterate("trk_pdhg_iterate_iso3", A, L, Groups::kIso3, N, frames, k_first, n_iters, sigma, tau, lam, lo, hi, fused, b, p, q, w,
+  return pdhg_iterate("trk_pdhg_iterate_iso3", A, L, Groups::kTriples, N, frames, k_first, n_iters, sigma, tau, lam, lo, hi, fused, b, p, q, w,
                       u, z, v, X, x_ld, keep_history, x_prev, xbar, x_true, NP, np_capacity_blocks, stream);
 }
 

@@ -1,5 +1,5 @@
 // pdhg_internal.h — one entry of the three PDHG updates (include/trk.h: the iteration and the eight sums), ONE definition for the
-// streaming kernels of pdhg.hip (float4 body and tail) and the fused first-difference kernels of tvops.hip: the same operations in
+// streaming kernels of pdhg.hip (float4 body and tail) and the fused first-difference kernels of pdhg_tv.hip: the same operations in
 // the same order, so the fused and the generic path leave the same bits.  Every multiply-add is an explicit fmaf and nothing else
 // may be contracted.
 #pragma once
@@ -92,21 +92,35 @@ __device__ __forceinline__ void pdhg_x_entry(float tau, float lo, float hi, floa
   if (xn == lo || xn == hi) s7 += 1.0;
 }
 
-// tvops.hip: the blocks (= rows of 8 partials) of the fused forms on a 2-D first-difference handle, 0 for any other handle
-int pdhg_tv_blocks(const trk_op* L);
-// tvops.hip: N of a 2-D first-difference handle, 0 for any other handle
-int pdhg_tv_size(const trk_op* L);
-// tvops.hip: the grouped part of the unfused isotropic dual — `frames` blocks of [H ; V] rows of an N x N image in u and q, pairs
-// through pdhg_q_pair, the last row's H and the last column's V through pdhg_q_entry.  pdhg_iso_blocks: the rows of partials it
-// writes (slots 1 and 3 of rows 0 .. blocks - 1).
-int pdhg_iso_blocks(int N, int frames);
-void pdhg_dual_q_iso_launch(int N, int frames, float sig, float lam, const float* u, float* q, double* partials, hipStream_t s);
-// tvops.hip: the space-time groups (h, v, t) of geometry (N, frames).  pdhg_iso3_blocks: the blocks (= rows of 8 partials) of ONE
-// launch over all frames, which the unfused dual, the fused dual and the fused primal share.  pdhg_dual_q_iso3_launch: the unfused
-// dual on u and q of frames 2 N (N - 1) + (frames - 1) N^2 rows, slots 1 and 3 of rows 0 .. blocks - 1.
-int pdhg_iso3_blocks(int N, int frames);
-void pdhg_dual_q_iso3_launch(int N, int frames, float sig, float lam, const float* u, float* q, double* partials, hipStream_t s);
-// tvops.hip: 1 and (N, frames) for a space-time handle whose frames all lie on this rank, 0 for any other handle
-int pdhg_st_geometry(const trk_op* L, int* N, int* frames);
+// How the rows of L are grouped in the dual update of q: every row alone (the l1 term), the pairs (h, v) of a pixel, or the
+// triples (h, v, t) of a voxel.  The one spelling of the mode for the loop of pdhg.hip and the kernels of pdhg_tv.hip.
+enum class Groups { kRows, kPairs, kTriples };
+
+// tvops.hip (tv_internal.h, which pdhg.hip cannot include beside vec_internal.h: both define NT): the kind and the geometry of a
+// first-difference handle with every frame on this rank, 0 for any other handle.  The fused forms of kRows and kPairs take the 2-D
+// handle (kind 3), those of kTriples the space-time handle (kind 4).
+int tv_geometry_of(const trk_op* L, int* N, int* frames);
+inline bool pdhg_fusable(const trk_op* L, Groups g, int* N, int* frames) {
+  return tv_geometry_of(L, N, frames) == (g == Groups::kTriples ? 4 : 3);
+}
+inline const char* pdhg_fusable_wanted(Groups g) {          // what TRK_EUNSUPPORTED says after the entry's name
+  return g == Groups::kTriples ? "the fused space-time forms take a handle from trk_spacetime_create with every frame on one rank"
+                               : "the fused forms take a handle from trk_deriv2d_create only";
+}
+
+// pdhg_tv.hip: the blocks (= rows of 8 partials) of ONE launch of a column-thread kernel on the groups g of geometry (N, frames);
+// the fused dual, the fused primal and the unfused grouped dual of a mode share the grid.
+int pdhg_tv_blocks(Groups g, int N, int frames);
+// pdhg_tv.hip: the unfused grouped dual (kPairs: `frames` blocks of [H ; V] rows; kTriples: the space-time rows) on u = L xbar and
+// q in memory, slots 1 and 3 of rows 0 .. blocks - 1.  No checks: trk_pdhg_dual_q_iso and trk_pdhg_dual_q_iso3 make them.
+void pdhg_grouped_dual_launch(Groups g, int N, int frames, float sig, float lam, const float* u, float* q, double* partials,
+                              hipStream_t s);
+// pdhg_tv.hip: the checked launches behind trk_pdhg_tv_dual, trk_pdhg_tv_dual_iso, trk_pdhg_st_dual_iso3 (g names the entry, and
+// the entry's name opens the error text) and behind trk_pdhg_tv_primal, trk_pdhg_st_primal (kTriples: the space-time one).
+int pdhg_fused_dual(Groups g, trk_op* L, double sigma, double lam, const float* xbar, float* q, double* partials, int capacity_blocks,
+                    int* n_blocks, trk_stream st);
+int pdhg_fused_primal(Groups g, trk_op* L, double tau, double lo, double hi, const float* x, const float* z, const float* q,
+                      float* x_new, float* xbar, const float* x_true, double* partials, int capacity_blocks, int* n_blocks,
+                      trk_stream st);
 
 }  // namespace trk

@@ -10,40 +10,18 @@
 // HBM-bound streaming stencils: 4n read + 8n write forward, 8n + 4n transposed; neighbours come from L1/L2.
 // For a time-sharded dynamic problem each rank owns whole frames; the temporal rows need the first frame of the next
 // rank (forward) and the last temporal block of the previous rank (transpose): trk_spacetime_set_halo.
-#include "trk_internal.h"
-#include "pdhg_internal.h"
+// PDHG's fused forms on these layouts: pdhg_tv.hip; what the two files share: tv_internal.h.
+#include "tv_internal.h"
 
 using namespace trk;
 
 namespace {
-
-constexpr int NT = 256;
-constexpr int RB = 4;              // image rows per thread and batch
-constexpr int kTvMaxBlocks = 4096;  // cap on the blocks (= block partials) per frame of the kernels that reduce
 
 inline int grid_for(int64_t n) {
   int64_t want = (n + NT - 1) / NT;
   const int64_t cap = kMaxPartialBlocks;
   if (want > cap) want = cap;
   return (int)(want < 1 ? 1 : want);
-}
-
-// The 2-D stencils run one thread per image COLUMN over batches of RB rows: every load of a batch is issued before the
-// first use (the kernels are latency-, then HBM-bound: memory-level parallelism is what fills the pipe), the vertical
-// neighbours of the batch are loaded once, row offsets are running sums (no integer division) and every load/store of a
-// wavefront is one contiguous row segment.  grid = (ceil(N/NT), row batches (grid-strided when capped), frames).
-struct Grid2 {
-  dim3 g;
-  int per_frame;  // blocks (= block partials) per frame
-};
-inline Grid2 grid2(int N, int frames, bool capped) {
-  const int gx = (N + NT - 1) / NT;
-  int gy = (N + RB - 1) / RB;
-  if (capped) {
-    const int cap = kTvMaxBlocks / gx;
-    if (gy > cap) gy = cap < 1 ? 1 : cap;
-  }
-  return {dim3(gx, gy, frames), gx * gy};
 }
 
 // blockIdx.z = frame / batch vector.  WEIGHTS: y = ((L2 x)^2 + eps2)^e instead of L2 x (k_tv_weights below).
@@ -117,39 +95,15 @@ __global__ __launch_bounds__(NT) void k_d2_adj(const float* __restrict__ y, int6
   const int j = blockIdx.x * NT + threadIdx.x;
   double ss = 0.0;
   if (j < N) {
-    const bool hr = j < N - 1, hl = j > 0;
     for (int i0 = blockIdx.y * RB; i0 < N; i0 += gridDim.y * RB) {
       const int64_t o0 = (int64_t)i0 * N + j;
-      const int64_t h0 = (int64_t)i0 * (N - 1) + j;
-      float hc[RB], hp[RB], v[RB + 1], a[RB], b[RB];
-#pragma unroll
-      for (int t = 0; t <= RB; ++t) {      // v[t] = yv[i0 + t - 1][j]
-        const int i = i0 + t - 1;
-        v[t] = (i >= 0 && i < N - 1) ? yv[o0 + (int64_t)(t - 1) * N] : 0.f;
-      }
-#pragma unroll
-      for (int t = 0; t < RB; ++t) {
-        const bool in = i0 + t < N;
-        hc[t] = (in && hr) ? yh[h0 + (int64_t)t * (N - 1)] : 0.f;
-        hp[t] = (in && hl) ? yh[h0 + (int64_t)t * (N - 1) - 1] : 0.f;
-        if (TEMPORAL) {
-          a[t] = (in && tc) ? tc[o0 + (int64_t)t * N] : 0.f;
-          b[t] = (in && tp) ? tp[o0 + (int64_t)t * N] : 0.f;
-        }
-      }
+      AdjGather<TEMPORAL> g;
+      g.load(yh, yv, tc, tp, N, i0, j);
 #pragma unroll
       for (int t = 0; t < RB; ++t) {
         const int i = i0 + t;
         if (i < N) {
-          float acc = 0.f;
-          if (hr) acc += hc[t];
-          if (hl) acc -= hp[t];
-          if (i < N - 1) acc += v[t + 1];
-          if (i > 0) acc -= v[t];
-          if (TEMPORAL) {
-            if (tc) acc += a[t];
-            if (tp) acc -= b[t];
-          }
+          const float acc = g.sum(t, i, N);
           out[o0 + (int64_t)t * N] = acc;
           if (SUMSQ) ss += (double)acc * acc;
         }
@@ -268,7 +222,7 @@ __global__ __launch_bounds__(NT) void k_tv_grad(const float* __restrict__ x, con
         if (hl) acc -= __fmul_rn(wp[t], xl[t] - c);
         if (i < N - 1) acc += __fmul_rn(v[t + 1], c - xc[t + 2]);
         if (i > 0) acc -= __fmul_rn(v[t], xc[t] - c);
-        if (tnext) acc += __fmul_rn(wn[t], c - xn[t]);             // same order as k_d2_adj<TEMPORAL>: + T_t - T_{t-1}
+        if (tnext) acc += __fmul_rn(wn[t], c - xn[t]);             // same order as AdjGather<true>::sum: + T_t - T_{t-1}
         if (tprev) acc -= __fmul_rn(wq[t], xp[t] - c);
         const float ov = RIN ? __fadd_rn(rr[t], __fmul_rn(lam, acc)) : __fmul_rn(lam, acc);   // (no contraction: the same bits with and without DOT)
         if (!DOT || live) out[o0 + (int64_t)t * N] = ov;
@@ -312,389 +266,6 @@ __global__ __launch_bounds__(NT) void k_time_fwd(const float* __restrict__ x, fl
   if (SUMSQ) {
     ss = block_sum<NT>(ss, red);
     if (threadIdx.x == 0) partials[(size_t)blockIdx.y * gridDim.x + blockIdx.x] = ss;
-  }
-}
-
-// Fused forms for PDHG (pdhg.hip; the entries: pdhg_internal.h), nothing of the length of L2 xbar or L2^T q touches memory:
-//   k_pdhg_tv_dual:    q' = clip(q + sig L2 xbar, -lam, lam), the differences formed in registers as k_d2_fwd forms them
-//                      (xbar read: 4n; q read and written: 8n + 8n); partials 1 (sum |L2 xbar|) and 3 (||q' - q||^2) of the block's row
-//                      <true>: isotropic TV, (H[i][j], V[i][j]) projected onto the 2-norm ball instead (partial 1: the sum of the
-//                      groups' 2-norms); the same bytes.  k_pdhg_dual_q_iso: that projection on a stored u = L xbar.
-//   k_pdhg_tv_primal:  x' = clip(x - tau (z + L2^T q), lo, hi), xbar' = 2 x' - x, L2^T q gathered in the order of k_d2_adj
-//                      (x, z, q read: 16n; x', xbar' written: 8n); partials 4 to 7
-// One thread per image column over batches of RB rows, as the stencils above; every thread stays to the block sums.
-//
-// One pixel's rows of the isotropic duals: the thread of column j holds both members of pixel (i, j)'s group.  pair: both exist
-// (i < N - 1 and j < N - 1), projected together; the last row's H and the last column's V are groups of one: the clip.
-__device__ __forceinline__ void pdhg_iso_pixel(bool has_h, bool has_v, float sig, float lam, float uh, float uv, float ph, float pv,
-                                               float* dh, float* dv, double& s1, double& s3) {
-  if (has_h && has_v) {
-    pdhg_q_pair(sig, lam, uh, uv, ph, pv, s1, s3);
-    *dh = ph;
-    *dv = pv;
-  } else if (has_h) {
-    *dh = pdhg_q_entry(sig, lam, uh, ph, s1, s3);
-  } else if (has_v) {
-    *dv = pdhg_q_entry(sig, lam, uv, pv, s1, s3);
-  }
-}
-
-// ISO: the isotropic dual (k_pdhg_tv_dual_iso of the documents), the same loads and stores, the H and V entry of a pixel joined.
-template <bool ISO>
-__global__ __launch_bounds__(NT) void k_pdhg_tv_dual(const float* __restrict__ xbar, float* q, int N, float sig, float lam,
-                                                     double* __restrict__ partials) {
-  __shared__ double red[NT / 64];
-  float* qh = q;
-  float* qv = q + (int64_t)N * (N - 1);
-  const int j = blockIdx.x * NT + threadIdx.x;
-  double s1 = 0.0, s3 = 0.0;
-  if (j < N) {
-    const bool hr = j < N - 1;
-    for (int i0 = blockIdx.y * RB; i0 < N; i0 += gridDim.y * RB) {
-      const int64_t o0 = (int64_t)i0 * N + j;
-      const int64_t h0 = (int64_t)i0 * (N - 1) + j;
-      float xc[RB + 1], xr[RB], ph[RB], pv[RB];
-#pragma unroll
-      for (int t = 0; t <= RB; ++t) xc[t] = (i0 + t < N) ? xbar[o0 + (int64_t)t * N] : 0.f;
-#pragma unroll
-      for (int t = 0; t < RB; ++t) {
-        const bool in = i0 + t < N;
-        xr[t] = (hr && in) ? xbar[o0 + (int64_t)t * N + 1] : 0.f;
-        ph[t] = (hr && in) ? qh[h0 + (int64_t)t * (N - 1)] : 0.f;
-        pv[t] = (i0 + t < N - 1) ? qv[o0 + (int64_t)t * N] : 0.f;
-      }
-#pragma unroll
-      for (int t = 0; t < RB; ++t) {
-        const int i = i0 + t;
-        if (i < N) {
-          if (ISO) {
-            pdhg_iso_pixel(hr, i < N - 1, sig, lam, xc[t] - xr[t], xc[t] - xc[t + 1], ph[t], pv[t], qh + h0 + (int64_t)t * (N - 1),
-                           qv + o0 + (int64_t)t * N, s1, s3);
-          } else {
-            if (hr) qh[h0 + (int64_t)t * (N - 1)] = pdhg_q_entry(sig, lam, xc[t] - xr[t], ph[t], s1, s3);
-            if (i < N - 1) qv[o0 + (int64_t)t * N] = pdhg_q_entry(sig, lam, xc[t] - xc[t + 1], pv[t], s1, s3);
-          }
-        }
-      }
-    }
-  }
-  s1 = block_sum<NT>(s1, red);
-  s3 = block_sum<NT>(s3, red);
-  if (threadIdx.x == 0) {
-    const size_t blk = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
-    partials[blk * 8 + 1] = s1;
-    partials[blk * 8 + 3] = s3;
-  }
-}
-
-// The unfused isotropic dual on u = L xbar in memory: `frames` blocks of [H ; V] rows (blockIdx.z = frame), the column-thread layout
-// of k_pdhg_tv_dual with u read where that kernel forms the differences.  Partials 1 and 3 of row (z gridDim.y + y) gridDim.x + x.
-__global__ __launch_bounds__(NT) void k_pdhg_dual_q_iso(const float* __restrict__ u, float* q, int N, float sig, float lam,
-                                                        double* __restrict__ partials) {
-  __shared__ double red[NT / 64];
-  const int64_t frame = (int64_t)blockIdx.z * 2 * N * (N - 1);
-  const float* __restrict__ uh = u + frame;
-  const float* __restrict__ uv = uh + (int64_t)N * (N - 1);
-  float* qh = q + frame;
-  float* qv = qh + (int64_t)N * (N - 1);
-  const int j = blockIdx.x * NT + threadIdx.x;
-  double s1 = 0.0, s3 = 0.0;
-  if (j < N) {
-    const bool hr = j < N - 1;
-    for (int i0 = blockIdx.y * RB; i0 < N; i0 += gridDim.y * RB) {
-      const int64_t o0 = (int64_t)i0 * N + j;
-      const int64_t h0 = (int64_t)i0 * (N - 1) + j;
-      float ah[RB], av[RB], ph[RB], pv[RB];
-#pragma unroll
-      for (int t = 0; t < RB; ++t) {
-        const bool in = i0 + t < N;
-        ah[t] = (hr && in) ? uh[h0 + (int64_t)t * (N - 1)] : 0.f;
-        ph[t] = (hr && in) ? qh[h0 + (int64_t)t * (N - 1)] : 0.f;
-        av[t] = (i0 + t < N - 1) ? uv[o0 + (int64_t)t * N] : 0.f;
-        pv[t] = (i0 + t < N - 1) ? qv[o0 + (int64_t)t * N] : 0.f;
-      }
-#pragma unroll
-      for (int t = 0; t < RB; ++t) {
-        const int i = i0 + t;
-        if (i < N)
-          pdhg_iso_pixel(hr, i < N - 1, sig, lam, ah[t], av[t], ph[t], pv[t], qh + h0 + (int64_t)t * (N - 1), qv + o0 + (int64_t)t * N,
-                         s1, s3);
-      }
-    }
-  }
-  s1 = block_sum<NT>(s1, red);
-  s3 = block_sum<NT>(s3, red);
-  if (threadIdx.x == 0) {
-    const size_t blk = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-    partials[blk * 8 + 1] = s1;
-    partials[blk * 8 + 3] = s3;
-  }
-}
-
-// x_new may be x (a pixel is read and then written by the same thread): no __restrict__ on the two
-template <bool HAS_XT>
-__global__ __launch_bounds__(NT) void k_pdhg_tv_primal(const float* x, const float* __restrict__ z, const float* __restrict__ q,
-                                                       float* x_new, float* __restrict__ xbar, const float* __restrict__ x_true, int N,
-                                                       float tau, float lo, float hi, double* __restrict__ partials) {
-  __shared__ double red[NT / 64];
-  const float* __restrict__ qh = q;
-  const float* __restrict__ qv = q + (int64_t)N * (N - 1);
-  const int j = blockIdx.x * NT + threadIdx.x;
-  double s4 = 0.0, s5 = 0.0, s6 = 0.0, s7 = 0.0;
-  if (j < N) {
-    const bool hr = j < N - 1, hl = j > 0;
-    for (int i0 = blockIdx.y * RB; i0 < N; i0 += gridDim.y * RB) {
-      const int64_t o0 = (int64_t)i0 * N + j;
-      const int64_t h0 = (int64_t)i0 * (N - 1) + j;
-      float hc[RB], hp[RB], v[RB + 1], xv[RB], zv[RB], tv[RB];
-#pragma unroll
-      for (int t = 0; t <= RB; ++t) {      // v[t] = qv[i0 + t - 1][j]
-        const int i = i0 + t - 1;
-        v[t] = (i >= 0 && i < N - 1) ? qv[o0 + (int64_t)(t - 1) * N] : 0.f;
-      }
-#pragma unroll
-      for (int t = 0; t < RB; ++t) {
-        const bool in = i0 + t < N;
-        hc[t] = (in && hr) ? qh[h0 + (int64_t)t * (N - 1)] : 0.f;
-        hp[t] = (in && hl) ? qh[h0 + (int64_t)t * (N - 1) - 1] : 0.f;
-        xv[t] = in ? x[o0 + (int64_t)t * N] : 0.f;
-        zv[t] = in ? z[o0 + (int64_t)t * N] : 0.f;
-        tv[t] = (HAS_XT && in) ? x_true[o0 + (int64_t)t * N] : 0.f;
-      }
-#pragma unroll
-      for (int t = 0; t < RB; ++t) {
-        const int i = i0 + t;
-        if (i < N) {
-          float acc = 0.f;                 // k_d2_adj's order
-          if (hr) acc += hc[t];
-          if (hl) acc -= hp[t];
-          if (i < N - 1) acc += v[t + 1];
-          if (i > 0) acc -= v[t];
-          float xn, xb;
-          pdhg_x_entry<HAS_XT>(tau, lo, hi, xv[t], zv[t] + acc, tv[t], xn, xb, s4, s5, s6, s7);
-          x_new[o0 + (int64_t)t * N] = xn;
-          xbar[o0 + (int64_t)t * N] = xb;
-        }
-      }
-    }
-  }
-  s4 = block_sum<NT>(s4, red);
-  s5 = block_sum<NT>(s5, red);
-  if (HAS_XT) s6 = block_sum<NT>(s6, red);
-  s7 = block_sum<NT>(s7, red);
-  if (threadIdx.x == 0) {
-    const size_t blk = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
-    partials[blk * 8 + 4] = s4;
-    partials[blk * 8 + 5] = s5;
-    partials[blk * 8 + 6] = HAS_XT ? s6 : 0.0;
-    partials[blk * 8 + 7] = s7;
-  }
-}
-
-// Fused forms for PDHG on the space-time operator with the groups (h, v, t) of a voxel (tv = 'iso3'; include/trk.h):
-//   k_pdhg_st_dual_iso3:  the group {H_t[i][j], V_t[i][j], T_t[i][j]} of q + sig L xbar projected onto the 2-norm ball of radius lam,
-//                         the three differences formed in registers as k_d2_fwd and k_time_fwd form them (xbar_t read, xbar_{t+1}
-//                         re-read: 4n to 8n; q read and written: 12n + 12n for rows ~ 3n); partials 1 and 3
-//   k_pdhg_dual_q_iso3:   the same projection on a stored u = L xbar, u read where the fused kernel forms a difference
-//   k_pdhg_st_primal:     k_pdhg_tv_primal with the temporal terms, L^T q gathered in the order of k_d2_adj<., true>
-//                         (x, z read: 8n, q read: 12n; x', xbar' written: 8n); partials 4 to 7; it knows nothing of the grouping
-// ONE launch over every frame: grid = (column blocks, row batches, frames), the row batches strided so that the launch has at most
-// max(kTvMaxBlocks, column blocks x frames) blocks — the partial buffer costs 64 bytes per block and iteration.  The three kernels
-// share the grid and write disjoint slots of row (z gridDim.y + y) gridDim.x + x.
-inline dim3 grid3(int N, int frames) {
-  const int gx = (N + NT - 1) / NT;
-  int gy = (N + RB - 1) / RB;
-  const int64_t cap = kTvMaxBlocks / ((int64_t)gx * frames);
-  if (gy > cap) gy = cap < 1 ? 1 : (int)cap;
-  return dim3(gx, gy, frames);
-}
-inline int grid3_blocks(int N, int frames) {
-  const dim3 g = grid3(N, frames);
-  return (int)(g.x * g.y * g.z);
-}
-
-// One voxel's rows: the thread of column j of frame t holds every member of voxel (t, i, j)'s group.  Three members: the triple; two:
-// pdhg_q_pair with the members in row order (h before v before t); one: the clip; the voxel (nt - 1, N - 1, N - 1) has no row.
-__device__ __forceinline__ void pdhg_iso3_voxel(bool has_h, bool has_v, bool has_t, float sig, float lam, float uh, float uv, float ut,
-                                                float ph, float pv, float pt, float* dh, float* dv, float* dt, double& s1, double& s3) {
-  if (has_h && has_v && has_t) {
-    pdhg_q_triple(sig, lam, uh, uv, ut, ph, pv, pt, s1, s3);
-    *dh = ph;
-    *dv = pv;
-    *dt = pt;
-  } else if (has_h && has_v) {
-    pdhg_q_pair(sig, lam, uh, uv, ph, pv, s1, s3);
-    *dh = ph;
-    *dv = pv;
-  } else if (has_h && has_t) {
-    pdhg_q_pair(sig, lam, uh, ut, ph, pt, s1, s3);
-    *dh = ph;
-    *dt = pt;
-  } else if (has_v && has_t) {
-    pdhg_q_pair(sig, lam, uv, ut, pv, pt, s1, s3);
-    *dv = pv;
-    *dt = pt;
-  } else if (has_h) {
-    *dh = pdhg_q_entry(sig, lam, uh, ph, s1, s3);
-  } else if (has_v) {
-    *dv = pdhg_q_entry(sig, lam, uv, pv, s1, s3);
-  } else if (has_t) {
-    *dt = pdhg_q_entry(sig, lam, ut, pt, s1, s3);
-  }
-}
-
-// FUSED: src = xbar (nt frames), the differences in registers; else src = u = L xbar with q's layout.  blockIdx.z = frame.
-template <bool FUSED>
-__device__ __forceinline__ void iso3_dual_body(const float* __restrict__ src, float* q, int N, int nt, float sig, float lam,
-                                               double* __restrict__ partials, double* red) {
-  const int f = blockIdx.z;
-  const int64_t npix = (int64_t)N * N, ps = 2 * (int64_t)N * (N - 1);
-  const bool ht = f < nt - 1;
-  float* qh = q + f * ps;
-  float* qv = qh + (int64_t)N * (N - 1);
-  float* qt = q + nt * ps + f * npix;                       // (read and written where ht only)
-  const float* __restrict__ xf = FUSED ? src + f * npix : src;            // FUSED: this frame and the next
-  const float* __restrict__ sh = FUSED ? src : src + f * ps;              // !FUSED: u laid out as q
-  const float* __restrict__ sv = FUSED ? src : sh + (int64_t)N * (N - 1);
-  const float* __restrict__ st = FUSED ? src : src + nt * ps + f * npix;
-  const int j = blockIdx.x * NT + threadIdx.x;
-  double s1 = 0.0, s3 = 0.0;
-  if (j < N) {
-    const bool hr = j < N - 1;
-    for (int i0 = blockIdx.y * RB; i0 < N; i0 += gridDim.y * RB) {
-      const int64_t o0 = (int64_t)i0 * N + j;
-      const int64_t h0 = (int64_t)i0 * (N - 1) + j;
-      float xc[RB + 1], ah[RB], at[RB], ph[RB], pv[RB], pt[RB];   // FUSED: ah = the right neighbour, at = the next frame
-      if (FUSED) {
-#pragma unroll
-        for (int t = 0; t <= RB; ++t) xc[t] = (i0 + t < N) ? xf[o0 + (int64_t)t * N] : 0.f;
-      } else {
-#pragma unroll
-        for (int t = 0; t < RB; ++t) xc[t] = (i0 + t < N - 1) ? sv[o0 + (int64_t)t * N] : 0.f;     // xc[t] = u_v
-      }
-#pragma unroll
-      for (int t = 0; t < RB; ++t) {
-        const bool in = i0 + t < N;
-        const int64_t o = o0 + (int64_t)t * N, hb = h0 + (int64_t)t * (N - 1);
-        if (FUSED) {
-          ah[t] = (hr && in) ? xf[o + 1] : 0.f;
-          at[t] = (ht && in) ? xf[npix + o] : 0.f;
-        } else {
-          ah[t] = (hr && in) ? sh[hb] : 0.f;
-          at[t] = (ht && in) ? st[o] : 0.f;
-        }
-        ph[t] = (hr && in) ? qh[hb] : 0.f;
-        pv[t] = (i0 + t < N - 1) ? qv[o] : 0.f;
-        pt[t] = (ht && in) ? qt[o] : 0.f;
-      }
-#pragma unroll
-      for (int t = 0; t < RB; ++t) {
-        const int i = i0 + t;
-        if (i < N) {
-          const int64_t o = o0 + (int64_t)t * N;
-          const float uh = FUSED ? xc[t] - ah[t] : ah[t];
-          const float uv = FUSED ? xc[t] - xc[t + 1] : xc[t];
-          const float ut = FUSED ? xc[t] - at[t] : at[t];
-          pdhg_iso3_voxel(hr, i < N - 1, ht, sig, lam, uh, uv, ut, ph[t], pv[t], pt[t], qh + h0 + (int64_t)t * (N - 1), qv + o, qt + o,
-                          s1, s3);
-        }
-      }
-    }
-  }
-  s1 = block_sum<NT>(s1, red);
-  s3 = block_sum<NT>(s3, red);
-  if (threadIdx.x == 0) {
-    const size_t blk = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-    partials[blk * 8 + 1] = s1;
-    partials[blk * 8 + 3] = s3;
-  }
-}
-
-__global__ __launch_bounds__(NT) void k_pdhg_st_dual_iso3(const float* __restrict__ xbar, float* q, int N, int nt, float sig, float lam,
-                                                          double* __restrict__ partials) {
-  __shared__ double red[NT / 64];
-  iso3_dual_body<true>(xbar, q, N, nt, sig, lam, partials, red);
-}
-
-__global__ __launch_bounds__(NT) void k_pdhg_dual_q_iso3(const float* __restrict__ u, float* q, int N, int nt, float sig, float lam,
-                                                         double* __restrict__ partials) {
-  __shared__ double red[NT / 64];
-  iso3_dual_body<false>(u, q, N, nt, sig, lam, partials, red);
-}
-
-// x_new may be x, as in k_pdhg_tv_primal.  blockIdx.z = frame; T_t at q + nt 2 N (N - 1) + t N^2.
-template <bool HAS_XT>
-__global__ __launch_bounds__(NT) void k_pdhg_st_primal(const float* x, const float* __restrict__ z, const float* __restrict__ q,
-                                                       float* x_new, float* __restrict__ xbar, const float* __restrict__ x_true, int N,
-                                                       int nt, float tau, float lo, float hi, double* __restrict__ partials) {
-  __shared__ double red[NT / 64];
-  const int f = blockIdx.z;
-  const int64_t npix = (int64_t)N * N, ps = 2 * (int64_t)N * (N - 1);
-  const float* __restrict__ qh = q + f * ps;
-  const float* __restrict__ qv = qh + (int64_t)N * (N - 1);
-  const float* __restrict__ qt = q + nt * ps;
-  const bool hc_t = f < nt - 1, hp_t = f > 0;                 // T_t and T_{t-1} exist
-  const float* __restrict__ tc = qt + f * npix;
-  const float* __restrict__ tp = qt + (f - 1) * npix;
-  x += f * npix;
-  z += f * npix;
-  x_new += f * npix;
-  xbar += f * npix;
-  if (HAS_XT) x_true += f * npix;
-  const int j = blockIdx.x * NT + threadIdx.x;
-  double s4 = 0.0, s5 = 0.0, s6 = 0.0, s7 = 0.0;
-  if (j < N) {
-    const bool hr = j < N - 1, hl = j > 0;
-    for (int i0 = blockIdx.y * RB; i0 < N; i0 += gridDim.y * RB) {
-      const int64_t o0 = (int64_t)i0 * N + j;
-      const int64_t h0 = (int64_t)i0 * (N - 1) + j;
-      float hc[RB], hp[RB], v[RB + 1], a[RB], b[RB], xv[RB], zv[RB], tv[RB];
-#pragma unroll
-      for (int t = 0; t <= RB; ++t) {      // v[t] = qv[i0 + t - 1][j]
-        const int i = i0 + t - 1;
-        v[t] = (i >= 0 && i < N - 1) ? qv[o0 + (int64_t)(t - 1) * N] : 0.f;
-      }
-#pragma unroll
-      for (int t = 0; t < RB; ++t) {
-        const bool in = i0 + t < N;
-        const int64_t o = o0 + (int64_t)t * N;
-        hc[t] = (in && hr) ? qh[h0 + (int64_t)t * (N - 1)] : 0.f;
-        hp[t] = (in && hl) ? qh[h0 + (int64_t)t * (N - 1) - 1] : 0.f;
-        a[t] = (in && hc_t) ? tc[o] : 0.f;
-        b[t] = (in && hp_t) ? tp[o] : 0.f;
-        xv[t] = in ? x[o] : 0.f;
-        zv[t] = in ? z[o] : 0.f;
-        tv[t] = (HAS_XT && in) ? x_true[o] : 0.f;
-      }
-#pragma unroll
-      for (int t = 0; t < RB; ++t) {
-        const int i = i0 + t;
-        if (i < N) {
-          float acc = 0.f;                 // k_d2_adj<., true>'s order
-          if (hr) acc += hc[t];
-          if (hl) acc -= hp[t];
-          if (i < N - 1) acc += v[t + 1];
-          if (i > 0) acc -= v[t];
-          if (hc_t) acc += a[t];
-          if (hp_t) acc -= b[t];
-          float xn, xb;
-          pdhg_x_entry<HAS_XT>(tau, lo, hi, xv[t], zv[t] + acc, tv[t], xn, xb, s4, s5, s6, s7);
-          x_new[o0 + (int64_t)t * N] = xn;
-          xbar[o0 + (int64_t)t * N] = xb;
-        }
-      }
-    }
-  }
-  s4 = block_sum<NT>(s4, red);
-  s5 = block_sum<NT>(s5, red);
-  if (HAS_XT) s6 = block_sum<NT>(s6, red);
-  s7 = block_sum<NT>(s7, red);
-  if (threadIdx.x == 0) {
-    const size_t blk = ((size_t)blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
-    partials[blk * 8 + 4] = s4;
-    partials[blk * 8 + 5] = s5;
-    partials[blk * 8 + 6] = HAS_XT ? s6 : 0.0;
-    partials[blk * 8 + 7] = s7;
   }
 }
 
@@ -923,124 +494,20 @@ int trk_spacetime_set_halo(trk_op* op, const float* x_next, const float* y_prev)
   return TRK_OK;
 }
 
-// ---- PDHG's fused forms (the 2-D operator only; pdhg.hip chains them)
-int trk_pdhg_fused_caps(const trk_op* L, int* can) {
-  TRK_REQUIRE(L && can, "trk_pdhg_fused_caps: NULL argument");
-  *can = L->kind == 3 ? 1 : 0;
-  return TRK_OK;
-}
-
-int trk_pdhg_tv_dual(trk_op* L, double sigma, double lam, const float* xbar, float* q, double* partials, int capacity_blocks,
-                     int* n_blocks, trk_stream st) {
-  TRK_REQUIRE(L && xbar && q && partials && n_blocks, "trk_pdhg_tv_dual: NULL argument");
-  if (L->kind != 3) return fail(TRK_EUNSUPPORTED, "trk_pdhg_tv_dual: the fused forms take a handle from trk_deriv2d_create only");
-  TRK_REQUIRE(sigma > 0.0 && sigma < __builtin_inf(), "trk_pdhg_tv_dual: sigma must be finite and > 0");
-  TRK_REQUIRE(lam >= 0.0 && lam < __builtin_inf(), "trk_pdhg_tv_dual: lam must be finite and >= 0");
-  TRK_REQUIRE(q != xbar, "trk_pdhg_tv_dual: q must not alias xbar");
-  const int N = static_cast<D2Impl*>(L->impl)->N;
-  const Grid2 g2 = grid2(N, 1, true);
-  TRK_REQUIRE(g2.per_frame <= capacity_blocks, "trk_pdhg_tv_dual: partial buffer too small (%d blocks needed)", g2.per_frame);
-  *n_blocks = g2.per_frame;
-  hipLaunchKernelGGL(k_pdhg_tv_dual<false>, g2.g, dim3(NT), 0, (hipStream_t)st, xbar, q, N, (float)sigma, (float)lam, partials);
-  TRK_LAUNCH_CHECK();
-  return TRK_OK;
-}
-
-int trk_pdhg_tv_dual_iso(trk_op* L, double sigma, double lam, const float* xbar, float* q, double* partials, int capacity_blocks,
-                         int* n_blocks, trk_stream st) {
-  TRK_REQUIRE(L && xbar && q && partials && n_blocks, "trk_pdhg_tv_dual_iso: NULL argument");
-  if (L->kind != 3) return fail(TRK_EUNSUPPORTED, "trk_pdhg_tv_dual_iso: the fused forms take a handle from trk_deriv2d_create only");
-  TRK_REQUIRE(sigma > 0.0 && sigma < __builtin_inf(), "trk_pdhg_tv_dual_iso: sigma must be finite and > 0");
-  TRK_REQUIRE(lam >= 0.0 && lam < __builtin_inf(), "trk_pdhg_tv_dual_iso: lam must be finite and >= 0");
-  TRK_REQUIRE(q != xbar, "trk_pdhg_tv_dual_iso: q must not alias xbar");
-  const int N = static_cast<D2Impl*>(L->impl)->N;
-  const Grid2 g2 = grid2(N, 1, true);
-  TRK_REQUIRE(g2.per_frame <= capacity_blocks, "trk_pdhg_tv_dual_iso: partial buffer too small (%d blocks needed)", g2.per_frame);
-  *n_blocks = g2.per_frame;
-  hipLaunchKernelGGL(k_pdhg_tv_dual<true>, g2.g, dim3(NT), 0, (hipStream_t)st, xbar, q, N, (float)sigma, (float)lam, partials);
-  TRK_LAUNCH_CHECK();
-  return TRK_OK;
-}
-
-int trk_pdhg_tv_primal(trk_op* L, double tau, double lo, double hi, const float* x, const float* z, const float* q, float* x_new,
-                       float* xbar, const float* x_true, double* partials, int capacity_blocks, int* n_blocks, trk_stream st) {
-  TRK_REQUIRE(L && x && z && q && x_new && xbar && partials && n_blocks, "trk_pdhg_tv_primal: NULL argument");
-  if (L->kind != 3) return fail(TRK_EUNSUPPORTED, "trk_pdhg_tv_primal: the fused forms take a handle from trk_deriv2d_create only");
-  TRK_REQUIRE(tau > 0.0 && tau < __builtin_inf(), "trk_pdhg_tv_primal: tau must be finite and > 0");
-  TRK_REQUIRE(lo <= hi, "trk_pdhg_tv_primal: need lo <= hi (either may be infinite)");
-  TRK_REQUIRE(xbar != x && xbar != x_new && xbar != z && xbar != q && xbar != x_true,
-              "trk_pdhg_tv_primal: xbar must not alias another operand");
-  TRK_REQUIRE(x_new != z && x_new != q && x_new != x_true, "trk_pdhg_tv_primal: x_new may alias x only");
-  const int N = static_cast<D2Impl*>(L->impl)->N;
-  const Grid2 g2 = grid2(N, 1, true);
-  TRK_REQUIRE(g2.per_frame <= capacity_blocks, "trk_pdhg_tv_primal: partial buffer too small (%d blocks needed)", g2.per_frame);
-  *n_blocks = g2.per_frame;
-  hipStream_t s = (hipStream_t)st;
-  if (x_true) hipLaunchKernelGGL((k_pdhg_tv_primal<true>), g2.g, dim3(NT), 0, s, x, z, q, x_new, xbar, x_true, N, (float)tau, (float)lo, (float)hi, partials);
-  else hipLaunchKernelGGL((k_pdhg_tv_primal<false>), g2.g, dim3(NT), 0, s, x, z, q, x_new, xbar, x_true, N, (float)tau, (float)lo, (float)hi, partials);
-  TRK_LAUNCH_CHECK();
-  return TRK_OK;
-}
-
-// ---- PDHG's fused forms on the space-time operator, the groups (h, v, t): a handle whose frames all lie on this rank
-static const char* const kStOnly = "the fused space-time forms take a handle from trk_spacetime_create with every frame on one rank";
-
-int trk_pdhg_st_dual_iso3(trk_op* L, double sigma, double lam, const float* xbar, float* q, double* partials, int capacity_blocks,
-                          int* n_blocks, trk_stream st) {
-  TRK_REQUIRE(L && xbar && q && partials && n_blocks, "trk_pdhg_st_dual_iso3: NULL argument");
-  int N = 0, nt = 0;
-  if (!pdhg_st_geometry(L, &N, &nt)) return fail(TRK_EUNSUPPORTED, "trk_pdhg_st_dual_iso3: %s", kStOnly);
-  TRK_REQUIRE(nt <= 65535, "trk_pdhg_st_dual_iso3: at most 65535 frames");
-  TRK_REQUIRE(sigma > 0.0 && sigma < __builtin_inf(), "trk_pdhg_st_dual_iso3: sigma must be finite and > 0");
-  TRK_REQUIRE(lam >= 0.0 && lam < __builtin_inf(), "trk_pdhg_st_dual_iso3: lam must be finite and >= 0");
-  TRK_REQUIRE(q != xbar, "trk_pdhg_st_dual_iso3: q must not alias xbar");
-  const int nb = grid3_blocks(N, nt);
-  TRK_REQUIRE(nb <= capacity_blocks, "trk_pdhg_st_dual_iso3: partial buffer too small (%d blocks needed)", nb);
-  *n_blocks = nb;
-  hipLaunchKernelGGL(k_pdhg_st_dual_iso3, grid3(N, nt), dim3(NT), 0, (hipStream_t)st, xbar, q, N, nt, (float)sigma, (float)lam, partials);
-  TRK_LAUNCH_CHECK();
-  return TRK_OK;
-}
-
-int trk_pdhg_st_primal(trk_op* L, double tau, double lo, double hi, const float* x, const float* z, const float* q, float* x_new,
-                       float* xbar, const float* x_true, double* partials, int capacity_blocks, int* n_blocks, trk_stream st) {
-  TRK_REQUIRE(L && x && z && q && x_new && xbar && partials && n_blocks, "trk_pdhg_st_primal: NULL argument");
-  int N = 0, nt = 0;
-  if (!pdhg_st_geometry(L, &N, &nt)) return fail(TRK_EUNSUPPORTED, "trk_pdhg_st_primal: %s", kStOnly);
-  TRK_REQUIRE(nt <= 65535, "trk_pdhg_st_primal: at most 65535 frames");
-  TRK_REQUIRE(tau > 0.0 && tau < __builtin_inf(), "trk_pdhg_st_primal: tau must be finite and > 0");
-  TRK_REQUIRE(lo <= hi, "trk_pdhg_st_primal: need lo <= hi (either may be infinite)");
-  TRK_REQUIRE(xbar != x && xbar != x_new && xbar != z && xbar != q && xbar != x_true,
-              "trk_pdhg_st_primal: xbar must not alias another operand");
-  TRK_REQUIRE(x_new != z && x_new != q && x_new != x_true, "trk_pdhg_st_primal: x_new may alias x only");
-  const int nb = grid3_blocks(N, nt);
-  TRK_REQUIRE(nb <= capacity_blocks, "trk_pdhg_st_primal: partial buffer too small (%d blocks needed)", nb);
-  *n_blocks = nb;
-  hipStream_t s = (hipStream_t)st;
-  const dim3 g = grid3(N, nt);
-  if (x_true) hipLaunchKernelGGL((k_pdhg_st_primal<true>), g, dim3(NT), 0, s, x, z, q, x_new, xbar, x_true, N, nt, (float)tau, (float)lo, (float)hi, partials);
-  else hipLaunchKernelGGL((k_pdhg_st_primal<false>), g, dim3(NT), 0, s, x, z, q, x_new, xbar, x_true, N, nt, (float)tau, (float)lo, (float)hi, partials);
-  TRK_LAUNCH_CHECK();
-  return TRK_OK;
-}
-
 }  // extern "C"
 
-int trk::pdhg_iso3_blocks(int N, int frames) { return grid3_blocks(N, frames); }
-void trk::pdhg_dual_q_iso3_launch(int N, int frames, float sig, float lam, const float* u, float* q, double* partials, hipStream_t s) {
-  hipLaunchKernelGGL(k_pdhg_dual_q_iso3, grid3(N, frames), dim3(NT), 0, s, u, q, N, frames, sig, lam, partials);
-}
-int trk::pdhg_st_geometry(const trk_op* L, int* N, int* frames) {
-  if (!L || L->kind != 4) return 0;
-  const auto* im = static_cast<const STImpl*>(L->impl);
-  if (im->has_next || im->has_prev) return 0;
-  *N = im->N;
-  *frames = im->nt;
-  return 1;
-}
-int trk::pdhg_tv_blocks(const trk_op* L) { return (L && L->kind == 3) ? grid2(static_cast<D2Impl*>(L->impl)->N, 1, true).per_frame : 0; }
-int trk::pdhg_tv_size(const trk_op* L) { return (L && L->kind == 3) ? static_cast<D2Impl*>(L->impl)->N : 0; }
-int trk::pdhg_iso_blocks(int N, int frames) { return grid2(N, 1, true).per_frame * frames; }
-void trk::pdhg_dual_q_iso_launch(int N, int frames, float sig, float lam, const float* u, float* q, double* partials, hipStream_t s) {
-  hipLaunchKernelGGL(k_pdhg_dual_q_iso, grid2(N, frames, true).g, dim3(NT), 0, s, u, q, N, sig, lam, partials);
+int trk::tv_geometry_of(const trk_op* L, int* N, int* frames) {
+  if (L && L->kind == 3) {
+    *N = static_cast<const D2Impl*>(L->impl)->N;
+    *frames = 1;
+    return 3;
+  }
+  if (L && L->kind == 4) {
+    const auto* im = static_cast<const STImpl*>(L->impl);
+    if (im->has_next || im->has_prev) return 0;
+    *N = im->N;
+    *frames = im->nt;
+    return 4;
+  }
+  return 0;
 }

@@ -710,150 +710,99 @@ class HipEngine:
         _lib.check(rc, "trk_mrnsd_iterate")
         return c.value
 
-    # ------------------------------------------------------------------ PDHG (pdhg.hip, tvops.hip; the rows of 8 partials: include/trk.h)
-    def pdhg_blocks(self, m, n, rows, fused_handle=None):
-        """The largest block count of an iteration's kernels: the capacity (in rows of 8 doubles) its partials need."""
+    # ------------------------------------------------------------------ PDHG (pdhg.hip, pdhg_tv.hip; the rows of 8 partials: include/trk.h)
+    def _pdhg(self, name, *args, stream=True):
+        """One library call of the PDHG family that reports an int (a block count) through its last pointer: a tensor goes as its
+        address and None as NULL, then the int's address and, for a call that launches, the stream.  Returns the int."""
         c = ctypes.c_int(0)
-        _lib.check(self.lib.trk_pdhg_blocks(int(m), int(n), int(rows), fused_handle, ctypes.byref(c)), "trk_pdhg_blocks")
+        _lib.check(getattr(self.lib, name)(*map(_ptr, args), ctypes.byref(c), *((self.stream(),) if stream else ())), name)
         return c.value
 
+    def _pdhg_iterate(self, name, hA, hL, geo, k_first, n_iters, sigma, tau, lam, lo, hi, fused, b, p, q, w, u, z, v, X, keep, x_prev, xbar,
+                      x_true, NP, np_cap):
+        """The three one-call loops: geo = () or (N, frames) behind the two handles."""
+        args = (hA, hL, *map(int, geo), int(k_first), int(n_iters), float(sigma), float(tau), float(lam), float(lo), float(hi),
+                int(bool(fused)), b, p, q, w, u, z, v, X, X.stride(0), int(bool(keep)), x_prev, xbar, x_true, NP, int(np_cap))
+        _lib.check(getattr(self.lib, name)(*map(_ptr, args), self.stream()), name)
+
+    def pdhg_blocks(self, m, n, rows, fused_handle=None):
+        """The largest block count of an iteration's kernels: the capacity (in rows of 8 doubles) its partials need."""
+        return self._pdhg("trk_pdhg_blocks", int(m), int(n), int(rows), fused_handle, stream=False)
+
     def pdhg_fused_caps(self, handle):
-        can = ctypes.c_int(0)
-        _lib.check(self.lib.trk_pdhg_fused_caps(handle, ctypes.byref(can)), "trk_pdhg_fused_caps")
-        return can.value
+        return self._pdhg("trk_pdhg_fused_caps", handle, stream=False)
 
     def pdhg_dual_p(self, sigma, w, b, p, partials, capacity):
         """p = (p + sigma (w - b)) / (1 + sigma) in place; slots 0, 2.  Returns the block count (as the four below)."""
-        c = ctypes.c_int(0)
-        rc = self.lib.trk_pdhg_dual_p(p.numel(), float(sigma), w.data_ptr(), b.data_ptr(), p.data_ptr(), _ptr(partials), int(capacity),
-                                      ctypes.byref(c), self.stream())
-        _lib.check(rc, "trk_pdhg_dual_p")
-        return c.value
+        return self._pdhg("trk_pdhg_dual_p", p.numel(), float(sigma), w, b, p, partials, int(capacity))
 
     def pdhg_dual_q(self, sigma, lam, u, q, partials, capacity):
         """q = clip(q + sigma u, -lam, lam) in place; slots 1, 3."""
-        c = ctypes.c_int(0)
-        rc = self.lib.trk_pdhg_dual_q(q.numel(), float(sigma), float(lam), u.data_ptr(), q.data_ptr(), _ptr(partials), int(capacity),
-                                      ctypes.byref(c), self.stream())
-        _lib.check(rc, "trk_pdhg_dual_q")
-        return c.value
+        return self._pdhg("trk_pdhg_dual_q", q.numel(), float(sigma), float(lam), u, q, partials, int(capacity))
 
     def pdhg_primal(self, tau, lo, hi, x, z, v, x_new, xbar, x_true, partials, capacity):
         """x_new = clip(x - tau (z + v), lo, hi), xbar = 2 x_new - x; v may be None; slots 4..7."""
-        c = ctypes.c_int(0)
-        rc = self.lib.trk_pdhg_primal(x.numel(), float(tau), float(lo), float(hi), x.data_ptr(), z.data_ptr(),
-                                      None if v is None else v.data_ptr(), x_new.data_ptr(), xbar.data_ptr(),
-                                      None if x_true is None else x_true.data_ptr(), _ptr(partials), int(capacity), ctypes.byref(c),
-                                      self.stream())
-        _lib.check(rc, "trk_pdhg_primal")
-        return c.value
+        return self._pdhg("trk_pdhg_primal", x.numel(), float(tau), float(lo), float(hi), x, z, v, x_new, xbar, x_true, partials,
+                          int(capacity))
 
     def pdhg_tv_dual(self, handle, sigma, lam, xbar, q, partials, capacity):
         """pdhg_dual_q with u = L xbar formed in registers (a FirstDerivative2D handle)."""
-        c = ctypes.c_int(0)
-        rc = self.lib.trk_pdhg_tv_dual(handle, float(sigma), float(lam), xbar.data_ptr(), q.data_ptr(), _ptr(partials), int(capacity),
-                                       ctypes.byref(c), self.stream())
-        _lib.check(rc, "trk_pdhg_tv_dual")
-        return c.value
+        return self._pdhg("trk_pdhg_tv_dual", handle, float(sigma), float(lam), xbar, q, partials, int(capacity))
 
     def pdhg_tv_primal(self, handle, tau, lo, hi, x, z, q, x_new, xbar, x_true, partials, capacity):
         """pdhg_primal with v = L^T q gathered in the kernel (a FirstDerivative2D handle)."""
-        c = ctypes.c_int(0)
-        rc = self.lib.trk_pdhg_tv_primal(handle, float(tau), float(lo), float(hi), x.data_ptr(), z.data_ptr(), q.data_ptr(),
-                                         x_new.data_ptr(), xbar.data_ptr(), None if x_true is None else x_true.data_ptr(),
-                                         _ptr(partials), int(capacity), ctypes.byref(c), self.stream())
-        _lib.check(rc, "trk_pdhg_tv_primal")
-        return c.value
+        return self._pdhg("trk_pdhg_tv_primal", handle, float(tau), float(lo), float(hi), x, z, q, x_new, xbar, x_true, partials,
+                          int(capacity))
 
     def pdhg_iterate(self, hA, hL, k_first, n_iters, sigma, tau, lam, lo, hi, fused, b, p, q, w, u, z, v, X, keep, x_prev, xbar,
                      x_true, NP, np_cap):
         """n_iters PDHG iterations in one library call."""
-        rc = self.lib.trk_pdhg_iterate(hA, hL, int(k_first), int(n_iters), float(sigma), float(tau), float(lam), float(lo), float(hi),
-                                       int(bool(fused)), b.data_ptr(), p.data_ptr(), q.data_ptr(), w.data_ptr(),
-                                       None if u is None else u.data_ptr(), z.data_ptr(), None if v is None else v.data_ptr(),
-                                       X.data_ptr(), X.stride(0), int(bool(keep)), x_prev.data_ptr(), xbar.data_ptr(),
-                                       None if x_true is None else x_true.data_ptr(), _ptr(NP), int(np_cap), self.stream())
-        _lib.check(rc, "trk_pdhg_iterate")
+        self._pdhg_iterate("trk_pdhg_iterate", hA, hL, (), k_first, n_iters, sigma, tau, lam, lo, hi, fused, b, p, q, w, u, z, v, X, keep,
+                           x_prev, xbar, x_true, NP, np_cap)
 
     # isotropic TV: the groups of geometry (N, frames) on the first-difference row layout (include/trk.h)
     def pdhg_blocks_iso(self, m, n, rows, N, frames, fused_handle=None):
         """pdhg_blocks for the isotropic forms."""
-        c = ctypes.c_int(0)
-        _lib.check(self.lib.trk_pdhg_blocks_iso(int(m), int(n), int(rows), int(N), int(frames), fused_handle, ctypes.byref(c)),
-                   "trk_pdhg_blocks_iso")
-        return c.value
+        return self._pdhg("trk_pdhg_blocks_iso", int(m), int(n), int(rows), int(N), int(frames), fused_handle, stream=False)
 
     def pdhg_dual_q_iso(self, N, frames, sigma, lam, u, q, partials, capacity):
         """q = each group of q + sigma u projected onto the 2-norm ball of radius lam, in place; slots 1, 3.  Returns the rows of
         partials that wrote (the grouped kernel's, then the tail's)."""
-        c = ctypes.c_int(0)
-        rc = self.lib.trk_pdhg_dual_q_iso(int(N), int(frames), q.numel(), float(sigma), float(lam), u.data_ptr(), q.data_ptr(),
-                                          _ptr(partials), int(capacity), ctypes.byref(c), self.stream())
-        _lib.check(rc, "trk_pdhg_dual_q_iso")
-        return c.value
+        return self._pdhg("trk_pdhg_dual_q_iso", int(N), int(frames), q.numel(), float(sigma), float(lam), u, q, partials, int(capacity))
 
     def pdhg_tv_dual_iso(self, handle, sigma, lam, xbar, q, partials, capacity):
         """pdhg_dual_q_iso with u = L xbar formed in registers (a FirstDerivative2D handle: geometry (N, 1))."""
-        c = ctypes.c_int(0)
-        rc = self.lib.trk_pdhg_tv_dual_iso(handle, float(sigma), float(lam), xbar.data_ptr(), q.data_ptr(), _ptr(partials),
-                                           int(capacity), ctypes.byref(c), self.stream())
-        _lib.check(rc, "trk_pdhg_tv_dual_iso")
-        return c.value
+        return self._pdhg("trk_pdhg_tv_dual_iso", handle, float(sigma), float(lam), xbar, q, partials, int(capacity))
 
     def pdhg_iterate_iso(self, hA, hL, N, frames, k_first, n_iters, sigma, tau, lam, lo, hi, fused, b, p, q, w, u, z, v, X, keep, x_prev,
                          xbar, x_true, NP, np_cap):
         """pdhg_iterate with the isotropic dual of geometry (N, frames)."""
-        rc = self.lib.trk_pdhg_iterate_iso(hA, hL, int(N), int(frames), int(k_first), int(n_iters), float(sigma), float(tau), float(lam),
-                                           float(lo), float(hi), int(bool(fused)), b.data_ptr(), p.data_ptr(), q.data_ptr(),
-                                           w.data_ptr(), None if u is None else u.data_ptr(), z.data_ptr(),
-                                           None if v is None else v.data_ptr(), X.data_ptr(), X.stride(0), int(bool(keep)),
-                                           x_prev.data_ptr(), xbar.data_ptr(), None if x_true is None else x_true.data_ptr(), _ptr(NP),
-                                           int(np_cap), self.stream())
-        _lib.check(rc, "trk_pdhg_iterate_iso")
+        self._pdhg_iterate("trk_pdhg_iterate_iso", hA, hL, (N, frames), k_first, n_iters, sigma, tau, lam, lo, hi, fused, b, p, q, w, u, z, v,
+                           X, keep, x_prev, xbar, x_true, NP, np_cap)
 
     # isotropic space-time TV: the groups (h, v, t) of geometry (N, frames) on the space-time row layout (include/trk.h)
     def pdhg_blocks_iso3(self, m, n, rows, N, frames, fused_handle=None):
         """pdhg_blocks for the space-time groups."""
-        c = ctypes.c_int(0)
-        _lib.check(self.lib.trk_pdhg_blocks_iso3(int(m), int(n), int(rows), int(N), int(frames), fused_handle, ctypes.byref(c)),
-                   "trk_pdhg_blocks_iso3")
-        return c.value
+        return self._pdhg("trk_pdhg_blocks_iso3", int(m), int(n), int(rows), int(N), int(frames), fused_handle, stream=False)
 
     def pdhg_dual_q_iso3(self, N, frames, sigma, lam, u, q, partials, capacity):
         """q = each group (h, v, t) of q + sigma u projected onto the 2-norm ball of radius lam, in place; slots 1, 3."""
-        c = ctypes.c_int(0)
-        rc = self.lib.trk_pdhg_dual_q_iso3(int(N), int(frames), q.numel(), float(sigma), float(lam), u.data_ptr(), q.data_ptr(),
-                                           _ptr(partials), int(capacity), ctypes.byref(c), self.stream())
-        _lib.check(rc, "trk_pdhg_dual_q_iso3")
-        return c.value
+        return self._pdhg("trk_pdhg_dual_q_iso3", int(N), int(frames), q.numel(), float(sigma), float(lam), u, q, partials, int(capacity))
 
     def pdhg_st_dual_iso3(self, handle, sigma, lam, xbar, q, partials, capacity):
         """pdhg_dual_q_iso3 with u = L xbar formed in registers (a single-rank SpaceTimeDerivative handle)."""
-        c = ctypes.c_int(0)
-        rc = self.lib.trk_pdhg_st_dual_iso3(handle, float(sigma), float(lam), xbar.data_ptr(), q.data_ptr(), _ptr(partials),
-                                            int(capacity), ctypes.byref(c), self.stream())
-        _lib.check(rc, "trk_pdhg_st_dual_iso3")
-        return c.value
+        return self._pdhg("trk_pdhg_st_dual_iso3", handle, float(sigma), float(lam), xbar, q, partials, int(capacity))
 
     def pdhg_st_primal(self, handle, tau, lo, hi, x, z, q, x_new, xbar, x_true, partials, capacity):
         """pdhg_primal with v = L^T q gathered in the kernel (a single-rank SpaceTimeDerivative handle)."""
-        c = ctypes.c_int(0)
-        rc = self.lib.trk_pdhg_st_primal(handle, float(tau), float(lo), float(hi), x.data_ptr(), z.data_ptr(), q.data_ptr(),
-                                         x_new.data_ptr(), xbar.data_ptr(), None if x_true is None else x_true.data_ptr(),
-                                         _ptr(partials), int(capacity), ctypes.byref(c), self.stream())
-        _lib.check(rc, "trk_pdhg_st_primal")
-        return c.value
+        return self._pdhg("trk_pdhg_st_primal", handle, float(tau), float(lo), float(hi), x, z, q, x_new, xbar, x_true, partials,
+                          int(capacity))
 
     def pdhg_iterate_iso3(self, hA, hL, N, frames, k_first, n_iters, sigma, tau, lam, lo, hi, fused, b, p, q, w, u, z, v, X, keep, x_prev,
                           xbar, x_true, NP, np_cap):
         """pdhg_iterate with the space-time groups of geometry (N, frames)."""
-        rc = self.lib.trk_pdhg_iterate_iso3(hA, hL, int(N), int(frames), int(k_first), int(n_iters), float(sigma), float(tau), float(lam),
-                                            float(lo), float(hi), int(bool(fused)), b.data_ptr(), p.data_ptr(), q.data_ptr(),
-                                            w.data_ptr(), None if u is None else u.data_ptr(), z.data_ptr(),
-                                            None if v is None else v.data_ptr(), X.data_ptr(), X.stride(0), int(bool(keep)),
-                                            x_prev.data_ptr(), xbar.data_ptr(), None if x_true is None else x_true.data_ptr(), _ptr(NP),
-                                            int(np_cap), self.stream())
-        _lib.check(rc, "trk_pdhg_iterate_iso3")
+        self._pdhg_iterate("trk_pdhg_iterate_iso3", hA, hL, (N, frames), k_first, n_iters, sigma, tau, lam, lo, hi, fused, b, p, q, w, u, z,
+                           v, X, keep, x_prev, xbar, x_true, NP, np_cap)
 
     def finalize_batched(self, partials, nblocks, nvals, batches, out, out_stride):
         rc = self.lib.trk_finalize_batched(_ptr(partials), int(nblocks), int(nvals), int(batches), _ptr(out), int(out_stride),
