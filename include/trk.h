@@ -478,7 +478,9 @@ int trk_cgls_x_update(int64_t n, const double* gamma, int gamma_n, const double*
  *   stored un-normalised (alpha_j v_j), as the Golub-Kahan recurrence produces them before its division.
  *   work (may be NULL): >= 3 (k_max + 1) + 4 device doubles, zero-initialised by the caller, kept between calls: when mu is
  *   unchanged and columns were only appended since the last call (the fixed-lambda hybrid iteration) only the new
- *   columns are rotated; anything else restarts from the first column. */
+ *   columns are rotated; anything else restarts from the first column.  The state's layout inside `work` depends on work_doubles
+ *   (three arrays of (work_doubles - 4) / 3 doubles behind four scalars): pass one buffer with the SAME work_doubles on every call,
+ *   or zero it before the size changes. */
 int trk_bidiag_tikhonov(const double* alpha_sq, int64_t alpha_stride, const double* beta_sq, int64_t beta_stride, int k,
                         double mu, const double* beta0_sq, double* y, int y_over_alpha, double* work, int work_doubles,
                         trk_stream stream);
@@ -955,7 +957,7 @@ int trk_wgram(const float* W, int64_t ld, int k, int64_t m, const float* w, cons
  * against V also takes V^T (A^T A r) and V^T (L^T L r) (trk_gemv_tn: 3 or 4 right-hand sides in one pass, out[q*k + j] = V[j] . rhs[q]);
  * the new vector is v_k = (r - V c) / rho, so row k of G = V^T M V follows from a = V^T (M r), c, s = r . M r and rho^2 = ||r - V c||^2:
  *   G[i][k] = G[k][i] = (a_i - (G c)_i) / rho ,  G[k][k] = (s - 2 c.a + c.(G c)) / rho^2 ,  rhs_k = (t - c . rhs) / rho  (t = r . A^T b)
- * (trk_gram_row_from_sweep; ldg >= k+1; rhs / t may be NULL).  c is of rounding size (r is the residual of the projected
+ * (trk_gram_row_from_sweep; ldg >= k+1; 1 <= k <= 2048, refused beyond; rhs / t may be NULL).  c is of rounding size (r is the residual of the projected
  * normal equations, orthogonal to V), so nothing cancels. */
 int trk_gemv_tn(const float* V, int64_t ld, int k, int64_t n, const float* const* rhs, int n_rhs, double* out_dev,
                 trk_stream stream);
@@ -968,8 +970,8 @@ int trk_gram_row_from_sweep(double* G_dev, int ldg, int k, const double* a_dev, 
  * trip inside the loop.
  *   Minv_dev == NULL: Cholesky from scratch in LDS, O(k^3), k <= 139 (MMGKS: both Gram matrices change every iteration);
  *   Minv_dev != NULL (row stride ldm >= k): the inverse of the leading k_from x k_from block of G_A + lam G_L, left there by the
- *     previous call with the same lam, is bordered by rows k_from .. k-1 — O(k^2) per new row, any k (GKS: the Gram matrices
- *     only grow).  k_from = 0 builds it from nothing. */
+ *     previous call with the same lam, is bordered by rows k_from .. k-1 — O(k^2) per new row, k <= 2048, refused beyond (GKS: the
+ *     Gram matrices only grow).  k_from = 0 builds it from nothing. */
 int trk_gram_tikhonov(const double* GA_dev, int lda, const double* GL_dev, int ldl, const double* c_dev, int k, double lam,
                       double* Minv_dev, int ldm, int k_from, double* y_dev, trk_stream stream);
 /* Hybrid-GMRES's projected problem on the device (Hybrid_GMRES.py:69-77 with a numeric regparam):

@@ -499,6 +499,7 @@ extern "C" int trk_gram_row_from_sweep(double* G, int ldg, int k, const double* 
                                        const double* rho2, double* rhs, const double* tb, trk_stream st) {
   TRK_REQUIRE(G && a && c && s_rr && rho2 && k >= 1 && ldg >= k + 1, "trk_gram_row_from_sweep: bad argument");
   TRK_REQUIRE(!rhs || tb, "trk_gram_row_from_sweep: rhs given without t = r . (A^T b)");
+  TRK_REQUIRE(k <= 2048, "trk_gram_row_from_sweep: k <= 2048 (k doubles of LDS)");
   hipLaunchKernelGGL(k_gram_row_from_sweep, dim3(1), dim3(256), (size_t)k * sizeof(double), (hipStream_t)st, G, ldg, k, a, c, s_rr, rho2, rhs, tb);
   TRK_LAUNCH_CHECK();
   return TRK_OK;
@@ -621,6 +622,7 @@ extern "C" int trk_gram_tikhonov(const double* GA, int lda, const double* GL, in
   TRK_REQUIRE(GA && GL && c && y && k >= 1 && lda >= k && ldl >= k, "trk_gram_tikhonov: bad argument");
   if (Minv) {
     TRK_REQUIRE(ldm >= k && k_from >= 0 && k_from <= k, "trk_gram_tikhonov: bordering form needs ldm >= k and 0 <= k_from <= k");
+    TRK_REQUIRE(k <= 2048, "trk_gram_tikhonov: bordering form needs k <= 2048 (3 k doubles of LDS)");
     hipLaunchKernelGGL(k_gram_tikhonov_border, dim3(1), dim3(256), 3 * (size_t)k * sizeof(double), (hipStream_t)st, GA, lda, GL, ldl,
                        c, k, k_from, lam, Minv, ldm, y);
     TRK_LAUNCH_CHECK();
