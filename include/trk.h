@@ -991,7 +991,12 @@ int trk_hess_tikhonov(double* H_dev, int ldh, double* G_dev, double* Minv_dev, i
  * in LDS what it needs of its neighbours' halo (p = t + beta p and w = A p on tile + halo) instead of waiting for them at a
  * kernel boundary; same buffers, scalar layout and results (to fp32 rounding of the partial sums' order) as
  * trk_cgls_iterate_fused (w is never stored).  trk_cgls_tiled_caps: *can = 1 for separable reflect-boundary PSFs up to 9 x 9 on images of at
- * least 16 x 16 whose tile count fits the norm-partial rows (np_capacity_blocks) and the PG / PD buffers (pcap). */
+ * least 16 x 16 whose tile count fits the norm-partial rows (np_capacity_blocks) and the PG / PD buffers (pcap) and is at most
+ * 1024, whatever capacities are passed (a kernel sums at most 1024 block partials of its producer); both entry points refuse a
+ * handle with more tiles (TRK_EUNSUPPORTED).  *n_g_inout: the valid gamma partials in PG, any count from 1 up to pcap (above pcap:
+ * TRK_EINVAL); more than 1024 of them — the caller's t_0 = A^T r_0 on a tall image — are summed by one extra finalize launch before
+ * the first iteration.  x_k = fmaf(alpha, p_k, x_{k-1}), one rounding, as the streaming x updates; the ||x_k - x_{k-1}||^2 partial
+ * is taken from (float)(alpha p_k). */
 int trk_cgls_tiled_caps(trk_op* A, int np_capacity_blocks, int pcap, int* can);
 int trk_cgls_iterate_tiled(trk_op* A, int k_first, int n_iters, float* P, int64_t p_ld, float* R, int64_t r_ld, float* t,
                            float* X, int64_t x_ld, int keep_history, const float* x_prev, const float* x_true, double* S,
@@ -1001,8 +1006,8 @@ int trk_cgls_iterate_tiled(trk_op* A, int k_first, int n_iters, float* P, int64_
 /* The same iteration with TWO blurs instead of four: w_k = A p_k is never blurred — it is A t_{k-1} + beta w_{k-1} (csrc/cgls_tiled.hip,
  * k_cgls_tile_a2 / _b2); ||w_k||^2 is measured on the vector itself.  p, w: n floats each, updated in place (w: any finite content
  * before the first iteration); R: [2][r_ld] ping-pong pair (iteration k reads index (k-1) & 1, writes k & 1); PG / PD: gamma / delta
- * block partials, `pcap` doubles each; *n_g_inout: valid gamma partials in PG (set by the caller's t_0 = A^T r_0).  Scalar layout
- * and everything else as trk_cgls_iterate_tiled. */
+ * block partials, `pcap` doubles each; *n_g_inout: valid gamma partials in PG (set by the caller's t_0 = A^T r_0), any count up to
+ * pcap.  At most 1024 tiles, the scalar layout and everything else as trk_cgls_iterate_tiled. */
 int trk_cgls_iterate_tiled2(trk_op* A, int k_first, int n_iters, float* p, float* w, float* R, int64_t r_ld, float* t, float* X,
                             int64_t x_ld, int keep_history, const float* x_prev, const float* x_true, double* S, double* PG,
                             double* PD, int pcap, double* NP, int np_capacity_blocks, int* n_g_inout, int* n_np_inout,

@@ -565,12 +565,27 @@ static const TiledCache* tiled_cache(trk_op* A) {
   return static_cast<const TiledCache*>(A->aux);
 }
 
+// The consumers of a scalar source read at most 64 * PMAX partials (partials_issue), so a tile count above that is refused, and gamma
+// partials handed in by the caller's t_0 = A^T r_0 beyond it (the sliding blur makes up to 3840 bands x spans) are summed once, by
+// the finalize kernel, into a stream-ordered scratch double: the first K_A then reads one value.  One small launch, in that case only.
+constexpr int kTiledMaxPartials = 64 * PMAX;
+static int gamma_source(const char* who, const double* PG, int n_g, int pcap, hipStream_t s, ScalarSrc* src) {
+  TRK_REQUIRE(n_g >= 0 && n_g <= pcap, "%s: %d gamma partials exceed the partial buffers (pcap = %d)", who, n_g, pcap);
+  *src = ScalarSrc{PG, n_g};
+  if (n_g <= kTiledMaxPartials) return TRK_OK;
+  double* one = nullptr;
+  if (int rc = scratch_doubles(s, 1, &one)) return rc;
+  if (int rc = finalize_sums(PG, n_g, 1, 1, one, s)) return rc;
+  *src = ScalarSrc{one, 1};
+  return TRK_OK;
+}
+
 int trk_cgls_tiled_caps(trk_op* A, int np_capacity_blocks, int pcap, int* can) {
   TRK_REQUIRE(A && can, "trk_cgls_tiled_caps: NULL argument");
   const TiledCache* c = tiled_cache(A);                    // (asked by every CGLS() call: must not touch the device after the first)
   *can = 0;
   if (!c) return TRK_EHIP;                                 // the error string is set; nothing was cached: the next call asks again
-  *can = (c->ntiles > 0 && c->ntiles <= np_capacity_blocks && c->ntiles <= pcap) ? 1 : 0;
+  *can = (c->ntiles > 0 && c->ntiles <= kTiledMaxPartials && c->ntiles <= np_capacity_blocks && c->ntiles <= pcap) ? 1 : 0;
   return TRK_OK;
 }
 
@@ -586,9 +601,13 @@ int trk_cgls_iterate_tiled(trk_op* A, int k_first, int n_iters, float* P, int64_
   if (tc->ntiles <= 0) return fail(TRK_EUNSUPPORTED, "trk_cgls_iterate_tiled: needs a reflect-boundary separable blur <= 9x9 on an image >= 16x16");
   const TiledGeom g = tc->g;
   const int ntiles = tc->ntiles;
+  if (ntiles > kTiledMaxPartials) return fail(TRK_EUNSUPPORTED, "trk_cgls_iterate_tiled: %d tiles, at most %d (images up to 1024 tiles of 32 x 32)", ntiles, kTiledMaxPartials);
   TRK_REQUIRE(ntiles <= np_capacity_blocks && ntiles <= pcap, "trk_cgls_iterate_tiled: %d tiles exceed the partial buffers", ntiles);
   hipStream_t s = (hipStream_t)stream;
   int n_g = *n_g_inout;
+  ScalarSrc gam{PG, n_g};
+  if (n_iters > 0)
+    if (int rc = gamma_source("trk_cgls_iterate_tiled", PG, n_g, pcap, s, &gam)) return rc;
   for (int k = k_first; k < k_first + n_iters; ++k) {
     const int64_t b = 5 * (int64_t)k;
     float *p_old = P + (int64_t)((k - 1) & 1) * p_ld, *p_new = P + (int64_t)(k & 1) * p_ld;
@@ -596,7 +615,7 @@ int trk_cgls_iterate_tiled(trk_op* A, int k_first, int n_iters, float* P, int64_
     const double* gprev = (k <= 2) ? S : S + 5 * (int64_t)(k - 2) + 1;      // gamma_{k-2}
     double* gpub = (k == 1) ? S : S + b - 4;                                 // gamma_{k-1} goes here
     float* x_new = X + (int64_t)(keep_history ? (k - 1) : ((k - 1) & 1)) * x_ld;
-    hipLaunchKernelGGL(k_cgls_tile_a, dim3(ntiles), dim3(NT), 0, s, g, t, p_old, p_new, ScalarSrc{PG, n_g}, gprev, gpub,
+    hipLaunchKernelGGL(k_cgls_tile_a, dim3(ntiles), dim3(NT), 0, s, g, t, p_old, p_new, gam, gprev, gpub,
                        k == 1 ? 1 : 0, PD);
     double* np = NP + 3 * (int64_t)ntiles * (k - 1);
     if (x_true)
@@ -607,6 +626,7 @@ int trk_cgls_iterate_tiled(trk_op* A, int k_first, int n_iters, float* P, int64_
                          ScalarSrc{PD, ntiles}, gpub, S + b, PG, np);
     TRK_LAUNCH_CHECK();
     n_g = ntiles;
+    gam = ScalarSrc{PG, n_g};
     x_prev = x_new;
   }
   *n_g_inout = n_g;
@@ -626,16 +646,20 @@ int trk_cgls_iterate_tiled2(trk_op* A, int k_first, int n_iters, float* p, float
   if (tc->ntiles <= 0) return fail(TRK_EUNSUPPORTED, "trk_cgls_iterate_tiled2: needs a reflect-boundary separable blur <= 9x9 on an image >= 16x16");
   const TiledGeom g = tc->g;
   const int ntiles = tc->ntiles;
+  if (ntiles > kTiledMaxPartials) return fail(TRK_EUNSUPPORTED, "trk_cgls_iterate_tiled2: %d tiles, at most %d (images up to 1024 tiles of 32 x 32)", ntiles, kTiledMaxPartials);
   TRK_REQUIRE(ntiles <= np_capacity_blocks && ntiles <= pcap, "trk_cgls_iterate_tiled2: %d tiles exceed the partial buffers", ntiles);
   hipStream_t s = (hipStream_t)stream;
   int n_g = *n_g_inout;
+  ScalarSrc gam{PG, n_g};
+  if (n_iters > 0)
+    if (int rc = gamma_source("trk_cgls_iterate_tiled2", PG, n_g, pcap, s, &gam)) return rc;
   for (int k = k_first; k < k_first + n_iters; ++k) {
     const int64_t b = 5 * (int64_t)k;
     float *r_old = R + (int64_t)((k - 1) & 1) * r_ld, *r_new = R + (int64_t)(k & 1) * r_ld;
     const double* gprev = (k <= 2) ? S : S + 5 * (int64_t)(k - 2) + 1;      // gamma_{k-2}
     double* gpub = (k == 1) ? S : S + b - 4;                                 // gamma_{k-1} goes here
     float* x_new = X + (int64_t)(keep_history ? (k - 1) : ((k - 1) & 1)) * x_ld;
-    hipLaunchKernelGGL(k_cgls_tile_a2, dim3(ntiles), dim3(NT), 0, s, g, t, p, w, ScalarSrc{PG, n_g}, gprev, gpub, k == 1 ? 1 : 0, PD);
+    hipLaunchKernelGGL(k_cgls_tile_a2, dim3(ntiles), dim3(NT), 0, s, g, t, p, w, gam, gprev, gpub, k == 1 ? 1 : 0, PD);
     double* np = NP + 3 * (int64_t)ntiles * (k - 1);
     if (x_true)
       hipLaunchKernelGGL(k_cgls_tile_b2<true>, dim3(ntiles), dim3(NT), 0, s, g, w, p, r_old, r_new, t, x_prev, x_new, x_true,
@@ -645,6 +669,7 @@ int trk_cgls_iterate_tiled2(trk_op* A, int k_first, int n_iters, float* p, float
                          ScalarSrc{PD, ntiles}, gpub, S + b, PG, np);
     TRK_LAUNCH_CHECK();
     n_g = ntiles;
+    gam = ScalarSrc{PG, n_g};
     x_prev = x_new;
   }
   *n_g_inout = n_g;
