@@ -666,6 +666,42 @@ int trk_mrnsd_iterate(trk_op* A, int k_first, int n_iters, float* g, float* s, f
                       int keep_history, const float* x_prev, const float* x_true, double* S, double* GB, int gb_capacity, double* NP,
                       int np_capacity_blocks, int* n_np_inout, double* PU, int pcap, trk_stream stream);
 
+/* ---------------------------------------------------------------- MLEM / Richardson-Lucy: Poisson data, x >= 0 --- */
+/* Maximise the Poisson likelihood of b ~ Poisson(A x + bg), bg >= 0 a known background (the scalar bg, or the m-vector bg_vec when that
+ * is not NULL): min KL(b, A x + bg) over x >= 0 with KL(b, y) = sum_i kl(b_i, y_i).  With s = A^T 1 and sinv_i = (s_i > 0) ? 1 / s_i : 0
+ * (an unknown no datum sees — a masked detector — gets sinv_i = 0 and x_i = 0 from the first iteration on), iteration k is
+ *   w = A x_{k-1} ;  rho = b / (w + bg) ;  t = A^T rho ;  x_k = x_{k-1} . t . sinv
+ * A^T is the operator's own transpose throughout (trk_op_apply(A, 1, ...)), also where that is not the adjoint.  Vectors fp32, sums
+ * fp64, no atomics.  The fp32 operations, in this order, nothing contracted (/ is the correctly rounded division):
+ *   ratio:   y = w + bg ;  rho = (y > 0) ? b / y : 0
+ *   update:  x' = fmaxf((x * t) * sinv, 0) ;  d = x' - x        (the clamp acts only where an operator has negative entries)
+ *   kl(b, y), in fp64 from the fp32 values:  (y - b) + b * log(b / y)  for b > 0, y > 0, both finite ;  y  for b == 0, y >= 0 ;
+ *            +inf otherwise (the point lies outside the domain of the likelihood).  No case gives a NaN.
+ * Sums: block partials in PDHG's ROWS OF 8 and PDHG's slot numbers — block j of a kernel writes its slots of partials[8 j .. 8 j + 7]
+ * and nothing else, the two kernels of an iteration share one zeroed block of 8 * capacity_blocks doubles, and
+ * trk_finalize_batched(NP, capacity, 8, iterations, S + 8, 8) leaves row k (1-based) at S + 8k:
+ *   [ KL(b, w + bg), ||w + bg - b||^2 ((y - b)^2 in fp64), 0, 0, ||x'||^2, ||d||^2, ||x' - x_true||^2 (0 without x_true),
+ *     the number of entries of x' equal to 0 ]
+ * Slots 0 and 1 describe x_{k-1}, the point iteration k applies A to: they cost no product of their own.
+ *
+ * trk_mlem_sinv: sinv from s by one streaming kernel (sinv may be s).
+ * trk_mlem_ratio (slots 0, 1; rho may be w and nothing else), trk_mlem_update (slots 4..7; x_new may be x and nothing else):
+ *   streaming kernels, 16-byte accesses where every operand is 16-byte aligned.  *n_blocks: the blocks that wrote.
+ * trk_mlem_blocks: the largest block count of an iteration's kernels.
+ * trk_mlem_iterate: iterations k_first .. k_first + n_iters - 1 enqueued by one call, nothing read back; four launches each (rho is
+ *   written over w).  Iteration k takes x_{k-1} from x_prev (k = k_first) or the slot it wrote, writes iterate k to slot k-1 of X
+ *   (keep_history) or (k-1) & 1, and its partials to NP + 8 np_capacity_blocks (k-1) (zeroed by the caller).  The same kernels as
+ *   stepping: the same bits. */
+int trk_mlem_blocks(int64_t m, int64_t n, int* blocks);
+int trk_mlem_sinv(int64_t n, const float* s, float* sinv, trk_stream stream);
+int trk_mlem_ratio(int64_t m, double bg, const float* bg_vec, const float* w, const float* b, float* rho, double* partials,
+                   int capacity_blocks, int* n_blocks, trk_stream stream);
+int trk_mlem_update(int64_t n, const float* x, const float* t, const float* sinv, const float* x_true, float* x_new, double* partials,
+                    int capacity_blocks, int* n_blocks, trk_stream stream);
+int trk_mlem_iterate(trk_op* A, int k_first, int n_iters, double bg, const float* bg_vec, const float* b, const float* sinv, float* w,
+                     float* t, float* X, int64_t x_ld, int keep_history, const float* x_prev, const float* x_true, double* NP,
+                     int np_capacity_blocks, trk_stream stream);
+
 /* ---------------------------------------------------------------- PDHG: TV / l1 under box constraints --- */
 /* The primal-dual hybrid gradient iteration (Chambolle and Pock 2011, algorithm 1, theta = 1) for
  *   min_x  1/2 ||A x - b||^2 + lam ||L x||_1   subject to  lo <= x <= hi.
@@ -756,7 +792,21 @@ int trk_mrnsd_iterate(trk_op* A, int k_first, int n_iters, float* g, float* s, f
  *   disjoint slots of partial row (z gridDim.y + y) gridDim.x + x.
  * trk_pdhg_blocks_iso3: trk_pdhg_blocks for these forms; L_fused must be such a handle (TRK_EUNSUPPORTED) of geometry (N, frames)
  *   (TRK_EINVAL).
- * trk_pdhg_iterate_iso3: trk_pdhg_iterate_iso's arguments.  Five launches with `fused`, eight without. */
+ * trk_pdhg_iterate_iso3: trk_pdhg_iterate_iso's arguments.  Five launches with `fused`, eight without.
+ *
+ * KULLBACK-LEIBLER DATA TERM: min_x KL(b, A x + bg) + lam R(L x) over the box, KL and the background bg / bg_vec as MLEM's above, R
+ * any of the three terms.  Only the dual update of p changes: with F(y) = KL(b, y + bg), F*(p) = sum -b log(1 - p) - bg p and
+ *   prox_{sigma F*}(z) = 1/2 (1 + z + sigma bg - sqrt((z + sigma bg - 1)^2 + 4 sigma b)).
+ * The fp32 operations, in this order, with c2 = (float)(2 sigma), c4 = (float)(4 sigma) (sqrtf and / correctly rounded):
+ *   y = w + bg ;  z = fmaf(sf, y, p) ;  d = z - 1 ;  r = sqrtf(fmaf(d, d, c4 * b))
+ *   p' = (d <= 0) ? fmaf(0.5, d - r, 1) : 1 - (c2 * b) / (d + r)
+ * — the second form is the first multiplied out by (d + r), which does not cancel for large z; b == 0 gives p' = min(z, 1).
+ * Slot 0 becomes KL(b, w + bg) by MLEM's kl (+inf where A xbar + bg leaves the domain: xbar is not confined to the box; the iteration
+ * itself is unaffected), slot 2 stays ||p' - p||^2.  q, the primal update, the other slots and the steps are as above.
+ * trk_pdhg_dual_p_kl: trk_pdhg_dual_p's kernel shape (slots 0, 2; p in place).
+ * trk_pdhg_iterate_data: the one loop behind the three entries above with the grouping and the data term as arguments: groups = 0
+ *   (rows; N and frames unused), 1 (pairs) or 2 (triples); data = 0 (least squares; bg and bg_vec unused: the bits of the three
+ *   entries above) or 1 (Kullback-Leibler); then trk_pdhg_iterate_iso3's arguments. */
 int trk_pdhg_blocks(int64_t m, int64_t n, int64_t rows, const trk_op* L_fused, int* blocks);
 int trk_pdhg_dual_p(int64_t m, double sigma, const float* w, const float* b, float* p, double* partials, int capacity_blocks,
                     int* n_blocks, trk_stream stream);
@@ -793,6 +843,12 @@ int trk_pdhg_iterate_iso3(trk_op* A, trk_op* L, int N, int frames, int k_first, 
                           double lo, double hi, int fused, const float* b, float* p, float* q, float* w, float* u, float* z, float* v,
                           float* X, int64_t x_ld, int keep_history, const float* x_prev, float* xbar, const float* x_true, double* NP,
                           int np_capacity_blocks, trk_stream stream);
+int trk_pdhg_dual_p_kl(int64_t m, double sigma, double bg, const float* bg_vec, const float* w, const float* b, float* p,
+                       double* partials, int capacity_blocks, int* n_blocks, trk_stream stream);
+int trk_pdhg_iterate_data(trk_op* A, trk_op* L, int groups, int N, int frames, int data, double bg, const float* bg_vec, int k_first,
+                          int n_iters, double sigma, double tau, double lam, double lo, double hi, int fused, const float* b, float* p,
+                          float* q, float* w, float* u, float* z, float* v, float* X, int64_t x_ld, int keep_history,
+                          const float* x_prev, float* xbar, const float* x_true, double* NP, int np_capacity_blocks, trk_stream stream);
 
 /* ---------------------------------------------------------------- tall-skinny basis ops */
 /* h[j] = sum_i w2[i] * V[j][i] * r[i], j < k  (w2 may be NULL = 1).  One pass over V.

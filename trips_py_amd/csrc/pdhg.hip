@@ -52,6 +52,38 @@ __global__ __launch_bounds__(NT) void k_pdhg_dual_p(int64_t m, float sig, float 
   }
 }
 
+// The dual of the Kullback-Leibler data term (pdhg_p_entry_kl): k_pdhg_dual_p's loads and stores, and bg or the vector bgv.
+template <bool VEC, bool BG_VEC>
+__global__ __launch_bounds__(NT) void k_pdhg_dual_p_kl(int64_t m, float sig, float c2, float c4, float bg, const float* __restrict__ bgv,
+                                                       const float* __restrict__ w, const float* __restrict__ b, float* p,
+                                                       double* __restrict__ partials) {
+  __shared__ double lds[NT / 64];
+  double s0 = 0.0, s2 = 0.0;
+  const int64_t tid = (int64_t)blockIdx.x * NT + threadIdx.x, nth = (int64_t)gridDim.x * NT;
+  int64_t tail = 0;
+  if (VEC) {
+    const int64_t m4 = m >> 2;
+    tail = m4 << 2;
+    for (int64_t i = tid; i < m4; i += nth) {
+      const float4 wv = ld4(w, i), bv = ld4(b, i);
+      const float4 gv = BG_VEC ? ld4(bgv, i) : make_float4(bg, bg, bg, bg);
+      float4 pv = ld4(p, i);
+      pv.x = pdhg_p_entry_kl(sig, c2, c4, wv.x, gv.x, bv.x, pv.x, s0, s2);
+      pv.y = pdhg_p_entry_kl(sig, c2, c4, wv.y, gv.y, bv.y, pv.y, s0, s2);
+      pv.z = pdhg_p_entry_kl(sig, c2, c4, wv.z, gv.z, bv.z, pv.z, s0, s2);
+      pv.w = pdhg_p_entry_kl(sig, c2, c4, wv.w, gv.w, bv.w, pv.w, s0, s2);
+      st4(p, i, pv);
+    }
+  }
+  for (int64_t i = tail + tid; i < m; i += nth) p[i] = pdhg_p_entry_kl(sig, c2, c4, w[i], BG_VEC ? bgv[i] : bg, b[i], p[i], s0, s2);
+  s0 = block_sum<NT>(s0, lds);
+  s2 = block_sum<NT>(s2, lds);
+  if (threadIdx.x == 0) {
+    partials[blockIdx.x * 8 + 0] = s0;
+    partials[blockIdx.x * 8 + 2] = s2;
+  }
+}
+
 template <bool VEC>
 __global__ __launch_bounds__(NT) void k_pdhg_dual_q(int64_t rows, float sig, float lam, const float* __restrict__ u, float* q,
                                                     double* __restrict__ partials) {
@@ -196,8 +228,11 @@ int grouped_dual_q(Groups g, int N, int frames, int64_t rows, double sigma, doub
 }
 
 // The loop of trk_pdhg_iterate, trk_pdhg_iterate_iso and trk_pdhg_iterate_iso3 (the groups of geometry (N, frames)).  Only the
-// dual update of q differs, and with `fused` the handle the two fused kernels belong to.
-int pdhg_iterate(const char* who, trk_op* A, trk_op* L, Groups groups, int N, int frames, int k_first, int n_iters, double sigma,
+// dual update of q differs, and with `fused` the handle the two fused kernels belong to.  data: kDataL2 (the least-squares dual of p)
+// or kDataKL (trk_pdhg_dual_p_kl with the background bg / bg_vec, which kDataL2 ignores).
+enum { kDataL2 = 0, kDataKL = 1 };
+int pdhg_iterate(const char* who, trk_op* A, trk_op* L, Groups groups, int N, int frames, int data, double bg, const float* bg_vec,
+                 int k_first, int n_iters, double sigma,
                  double tau, double lam, double lo, double hi, int fused, const float* b, float* p, float* q, float* w, float* u, float* z,
                  float* v, float* X, int64_t x_ld, int keep_history, const float* x_prev, float* xbar, const float* x_true, double* NP,
                  int np_capacity_blocks, trk_stream stream) {
@@ -225,7 +260,9 @@ int pdhg_iterate(const char* who, trk_op* A, trk_op* L, Groups groups, int N, in
     float* x_new = X + (int64_t)(keep_history ? (k - 1) : ((k - 1) & 1)) * x_ld;
     int nb = 0, rc;
     if ((rc = trk_op_apply(A, 0, xbar, 0, w, 0, 1, nullptr, stream))) return rc;                       // w = A xbar
-    if ((rc = trk_pdhg_dual_p(m, sigma, w, b, p, part, np_capacity_blocks, &nb, stream))) return rc;
+    rc = data == kDataKL ? trk_pdhg_dual_p_kl(m, sigma, bg, bg_vec, w, b, p, part, np_capacity_blocks, &nb, stream)
+                         : trk_pdhg_dual_p(m, sigma, w, b, p, part, np_capacity_blocks, &nb, stream);
+    if (rc) return rc;
     if (fused) {
       rc = pdhg_fused_dual(groups, L, sigma, lam, xbar, q, part, np_capacity_blocks, &nb, stream);
     } else {
@@ -269,6 +306,24 @@ int trk_pdhg_dual_p(int64_t m, double sigma, const float* w, const float* b, flo
     hipLaunchKernelGGL((k_pdhg_dual_p<VEC>), dim3(grid), dim3(NT), 0, (hipStream_t)st, m, (float)sigma, (float)(1.0 / (1.0 + sigma)), w, b,
                        p, partials);
   }, aligned16(w) && aligned16(b) && aligned16(p));
+  TRK_LAUNCH_CHECK();
+  return TRK_OK;
+}
+
+int trk_pdhg_dual_p_kl(int64_t m, double sigma, double bg, const float* bg_vec, const float* w, const float* b, float* p, double* partials,
+                       int capacity_blocks, int* n_blocks, trk_stream st) {
+  TRK_REQUIRE(w && b && p && partials && n_blocks, "trk_pdhg_dual_p_kl: NULL argument");
+  TRK_REQUIRE(m >= 1, "trk_pdhg_dual_p_kl: need m >= 1");
+  TRK_REQUIRE(finite_pos(sigma), "trk_pdhg_dual_p_kl: sigma must be finite and > 0");
+  TRK_REQUIRE(bg_vec || (bg >= 0.0 && bg < __builtin_inf()), "trk_pdhg_dual_p_kl: the background must be finite and >= 0");
+  TRK_REQUIRE(p != w && p != b && p != bg_vec, "trk_pdhg_dual_p_kl: p must not alias w, b or bg_vec");
+  const int grid = stream_grid(m);
+  TRK_REQUIRE(grid <= capacity_blocks, "trk_pdhg_dual_p_kl: partial buffer too small (%d blocks needed)", grid);
+  *n_blocks = grid;
+  with_bools([&](auto VEC, auto BG_VEC) {
+    hipLaunchKernelGGL((k_pdhg_dual_p_kl<VEC, BG_VEC>), dim3(grid), dim3(NT), 0, (hipStream_t)st, m, (float)sigma, (float)(2.0 * sigma),
+                       (float)(4.0 * sigma), (float)bg, bg_vec, w, b, p, partials);
+  }, aligned16(w) && aligned16(b) && aligned16(p) && (!bg_vec || aligned16(bg_vec)), bg_vec != nullptr);
   TRK_LAUNCH_CHECK();
   return TRK_OK;
 }
@@ -325,8 +380,8 @@ int trk_pdhg_iterate(trk_op* A, trk_op* L, int k_first, int n_iters, double sigm
                      int fused, const float* b, float* p, float* q, float* w, float* u, float* z, float* v, float* X, int64_t x_ld,
                      int keep_history, const float* x_prev, float* xbar, const float* x_true, double* NP, int np_capacity_blocks,
                      trk_stream stream) {
-  return pdhg_iterate("trk_pdhg_iterate", A, L, Groups::kRows, 0, 0, k_first, n_iters, sigma, tau, lam, lo, hi, fused, b, p, q, w, u, z, v, X,
-                      x_ld, keep_history, x_prev, xbar, x_true, NP, np_capacity_blocks, stream);
+  return pdhg_iterate("trk_pdhg_iterate", A, L, Groups::kRows, 0, 0, kDataL2, 0.0, nullptr, k_first, n_iters, sigma, tau, lam, lo, hi,
+                      fused, b, p, q, w, u, z, v, X, x_ld, keep_history, x_prev, xbar, x_true, NP, np_capacity_blocks, stream);
 }
 
 int trk_pdhg_iterate_iso(trk_op* A, trk_op* L, int N, int frames, int k_first, int n_iters, double sigma, double tau, double lam,
@@ -334,8 +389,8 @@ int trk_pdhg_iterate_iso(trk_op* A, trk_op* L, int N, int frames, int k_first, i
                          float* X, int64_t x_ld, int keep_history, const float* x_prev, float* xbar, const float* x_true, double* NP,
                          int np_capacity_blocks, trk_stream stream) {
   TRK_REQUIRE(N >= 2 && frames >= 1, "trk_pdhg_iterate_iso: need N >= 2, frames >= 1");
-  return pdhg_iterate("trk_pdhg_iterate_iso", A, L, Groups::kPairs, N, frames, k_first, n_iters, sigma, tau, lam, lo, hi, fused, b, p, q, w, u, z,
-                      v, X, x_ld, keep_history, x_prev, xbar, x_true, NP, np_capacity_blocks, stream);
+  return pdhg_iterate("trk_pdhg_iterate_iso", A, L, Groups::kPairs, N, frames, kDataL2, 0.0, nullptr, k_first, n_iters, sigma, tau, lam,
+                      lo, hi, fused, b, p, q, w, u, z, v, X, x_ld, keep_history, x_prev, xbar, x_true, NP, np_capacity_blocks, stream);
 }
 
 int trk_pdhg_blocks_iso3(int64_t m, int64_t n, int64_t rows, int N, int frames, const trk_op* L_fused, int* blocks) {
@@ -352,8 +407,22 @@ int trk_pdhg_iterate_iso3(trk_op* A, trk_op* L, int N, int frames, int k_first, 
                           float* X, int64_t x_ld, int keep_history, const float* x_prev, float* xbar, const float* x_true, double* NP,
                           int np_capacity_blocks, trk_stream stream) {
   TRK_REQUIRE(N >= 2 && frames >= 1, "trk_pdhg_iterate_iso3: need N >= 2, frames >= 1");
-  return pdhg_iterate("trk_pdhg_iterate_iso3", A, L, Groups::kTriples, N, frames, k_first, n_iters, sigma, tau, lam, lo, hi, fused, b, p, q, w,
-                      u, z, v, X, x_ld, keep_history, x_prev, xbar, x_true, NP, np_capacity_blocks, stream);
+  return pdhg_iterate("trk_pdhg_iterate_iso3", A, L, Groups::kTriples, N, frames, kDataL2, 0.0, nullptr, k_first, n_iters, sigma, tau,
+                      lam, lo, hi, fused, b, p, q, w, u, z, v, X, x_ld, keep_history, x_prev, xbar, x_true, NP, np_capacity_blocks, stream);
+}
+
+int trk_pdhg_iterate_data(trk_op* A, trk_op* L, int groups, int N, int frames, int data, double bg, const float* bg_vec, int k_first,
+                          int n_iters, double sigma, double tau, double lam, double lo, double hi, int fused, const float* b, float* p,
+                          float* q, float* w, float* u, float* z, float* v, float* X, int64_t x_ld, int keep_history, const float* x_prev,
+                          float* xbar, const float* x_true, double* NP, int np_capacity_blocks, trk_stream stream) {
+  TRK_REQUIRE(groups >= 0 && groups <= 2, "trk_pdhg_iterate_data: groups is 0 (rows), 1 (pairs) or 2 (triples)");
+  TRK_REQUIRE(data == kDataL2 || data == kDataKL, "trk_pdhg_iterate_data: data is 0 (least squares) or 1 (Kullback-Leibler)");
+  TRK_REQUIRE(groups == 0 || (N >= 2 && frames >= 1), "trk_pdhg_iterate_data: need N >= 2, frames >= 1");
+  TRK_REQUIRE(data == kDataL2 || bg_vec || (bg >= 0.0 && bg < __builtin_inf()),
+              "trk_pdhg_iterate_data: the background must be finite and >= 0");
+  return pdhg_iterate("trk_pdhg_iterate_data", A, L, (Groups)groups, groups ? N : 0, groups ? frames : 0, data, bg, bg_vec, k_first, n_iters,
+                      sigma, tau, lam, lo, hi, fused, b, p, q, w, u, z, v, X, x_ld, keep_history, x_prev, xbar, x_true, NP,
+                      np_capacity_blocks, stream);
 }
 
 }  // extern "C"

@@ -4,6 +4,7 @@
 // may be contracted.
 #pragma once
 #include "trk_internal.h"
+#include "kl_internal.h"
 
 namespace trk {
 
@@ -14,6 +15,25 @@ __device__ __forceinline__ float pdhg_p_entry(float sig, float c, float w, float
   const float pn = fmaf(sig, e, p) * c;
   const double dp = (double)pn - (double)p;
   s0 += (double)e * (double)e;
+  s2 += dp * dp;
+  return pn;
+}
+
+// dual of the Kullback-Leibler data term KL(b, y + bg): the prox of sigma F* at z = p + sigma (w + bg), F*(p) = sum -b log(1 - p) - bg p,
+//   p' = 1/2 (1 + z - sqrt((z - 1)^2 + 4 sigma b)), in a form that does not cancel for large z.  c2 = (float)(2 sigma), c4 = (float)(4 sigma):
+//   y = w + bg ; z = fmaf(sig, y, p) ; d = z - 1 ; r = sqrtf(fmaf(d, d, c4 * b))
+//   p' = (d <= 0) ? fmaf(0.5, d - r, 1) : 1 - (c2 * b) / (d + r)          (b = 0: p' = min(z, 1))
+//   s0 += kl(b, y) (kl_internal.h: +inf where y leaves the domain, the update itself is unaffected), s2 += (p' - p)^2
+__device__ __forceinline__ float pdhg_p_entry_kl(float sig, float c2, float c4, float w, float bg, float b, float p, double& s0,
+                                                 double& s2) {
+#pragma clang fp contract(off)
+  const float y = w + bg;
+  const float z = fmaf(sig, y, p);
+  const float d = z - 1.f;
+  const float r = sqrtf(fmaf(d, d, c4 * b));
+  const float pn = (d <= 0.f) ? fmaf(0.5f, d - r, 1.f) : 1.f - (c2 * b) / (d + r);
+  const double dp = (double)pn - (double)p;
+  s0 += kl_term(b, y);
   s2 += dp * dp;
   return pn;
 }

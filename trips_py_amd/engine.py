@@ -710,6 +710,34 @@ class HipEngine:
         _lib.check(rc, "trk_mrnsd_iterate")
         return c.value
 
+    # ------------------------------------------------------------------ MLEM (mlem.hip; the rows of 8 partials: include/trk.h)
+    @staticmethod
+    def _background(bg):
+        """(scalar, vector) of a background given as a number or as a device vector."""
+        return (0.0, bg) if hasattr(bg, "data_ptr") else (float(bg), None)
+
+    def mlem_blocks(self, m, n):
+        """The largest block count of an iteration's kernels: the capacity (in rows of 8 doubles) its partials need."""
+        return self._pdhg("trk_mlem_blocks", int(m), int(n), stream=False)
+
+    def mlem_sinv(self, s, sinv):
+        """sinv = 1 / s where s > 0, else 0 (sinv may be s)."""
+        _lib.check(self.lib.trk_mlem_sinv(s.numel(), s.data_ptr(), sinv.data_ptr(), self.stream()), "trk_mlem_sinv")
+
+    def mlem_ratio(self, bg, w, b, rho, partials, capacity):
+        """rho = b / (w + bg) where w + bg > 0, else 0 (rho may be w; bg a number or a device vector); slots 0, 1.  Returns the block count."""
+        return self._pdhg("trk_mlem_ratio", w.numel(), *self._background(bg), w, b, rho, partials, int(capacity))
+
+    def mlem_update(self, x, t, sinv, x_true, x_new, partials, capacity):
+        """x_new = max(x t sinv, 0) (x_new may be x); slots 4..7.  Returns the block count."""
+        return self._pdhg("trk_mlem_update", x.numel(), x, t, sinv, x_true, x_new, partials, int(capacity))
+
+    def mlem_iterate(self, handle, k_first, n_iters, bg, b, sinv, w, t, X, keep, x_prev, x_true, NP, np_cap):
+        """n_iters MLEM iterations in one library call."""
+        args = (handle, int(k_first), int(n_iters), *self._background(bg), b, sinv, w, t, X, X.stride(0), int(bool(keep)), x_prev, x_true,
+                NP, int(np_cap))
+        _lib.check(self.lib.trk_mlem_iterate(*map(_ptr, args), self.stream()), "trk_mlem_iterate")
+
     # ------------------------------------------------------------------ PDHG (pdhg.hip, pdhg_tv.hip; the rows of 8 partials: include/trk.h)
     def _pdhg(self, name, *args, stream=True):
         """One library call of the PDHG family that reports an int (a block count) through its last pointer: a tensor goes as its
@@ -719,9 +747,11 @@ class HipEngine:
         return c.value
 
     def _pdhg_iterate(self, name, hA, hL, geo, k_first, n_iters, sigma, tau, lam, lo, hi, fused, b, p, q, w, u, z, v, X, keep, x_prev, xbar,
-                      x_true, NP, np_cap):
-        """The three one-call loops: geo = () or (N, frames) behind the two handles."""
-        args = (hA, hL, *map(int, geo), int(k_first), int(n_iters), float(sigma), float(tau), float(lam), float(lo), float(hi),
+                      x_true, NP, np_cap, background=None):
+        """The one-call loops: geo = () or (N, frames) behind the two handles; trk_pdhg_iterate_data: (groups, N, frames, data) and,
+        behind them, the background."""
+        bg = () if background is None else self._background(background)
+        args = (hA, hL, *map(int, geo), *bg, int(k_first), int(n_iters), float(sigma), float(tau), float(lam), float(lo), float(hi),
                 int(bool(fused)), b, p, q, w, u, z, v, X, X.stride(0), int(bool(keep)), x_prev, xbar, x_true, NP, int(np_cap))
         _lib.check(getattr(self.lib, name)(*map(_ptr, args), self.stream()), name)
 
@@ -803,6 +833,17 @@ class HipEngine:
         """pdhg_iterate with the space-time groups of geometry (N, frames)."""
         self._pdhg_iterate("trk_pdhg_iterate_iso3", hA, hL, (N, frames), k_first, n_iters, sigma, tau, lam, lo, hi, fused, b, p, q, w, u, z,
                            v, X, keep, x_prev, xbar, x_true, NP, np_cap)
+
+    # the Kullback-Leibler data term (include/trk.h): another dual of p, and the one loop with the grouping and the data term as arguments
+    def pdhg_dual_p_kl(self, sigma, bg, w, b, p, partials, capacity):
+        """p = the prox of sigma F* for F(y) = KL(b, y + bg) at p + sigma (w + bg), in place (bg a number or a device vector); slots 0, 2."""
+        return self._pdhg("trk_pdhg_dual_p_kl", p.numel(), float(sigma), *self._background(bg), w, b, p, partials, int(capacity))
+
+    def pdhg_iterate_data(self, hA, hL, groups, N, frames, data, bg, k_first, n_iters, sigma, tau, lam, lo, hi, fused, b, p, q, w, u, z, v,
+                          X, keep, x_prev, xbar, x_true, NP, np_cap):
+        """pdhg_iterate with groups = 0 / 1 / 2 (rows, pairs, triples of geometry (N, frames)) and data = 0 / 1 (least squares, KL)."""
+        self._pdhg_iterate("trk_pdhg_iterate_data", hA, hL, (groups, N, frames, data), k_first, n_iters, sigma, tau, lam, lo, hi, fused, b,
+                           p, q, w, u, z, v, X, keep, x_prev, xbar, x_true, NP, np_cap, background=bg)
 
     def finalize_batched(self, partials, nblocks, nvals, batches, out, out_stride):
         rc = self.lib.trk_finalize_batched(_ptr(partials), int(nblocks), int(nvals), int(batches), _ptr(out), int(out_stride),

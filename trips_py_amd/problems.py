@@ -204,3 +204,15 @@ def add_noise(b_true, level, seed=1):
     e = rng.standard_normal(b_true.shape)
     e *= level * np.linalg.norm(b_true) / np.linalg.norm(e)
     return b_true + e, float(np.linalg.norm(e))
+
+
+def poisson_noise(b_true, peak=None, background=0.0, seed=1):
+    """Seeded Poisson counts (float64, the shape of b_true) with mean peak * b_true / max(b_true) + background; peak=None: the mean is
+    b_true + background.  b_true and background must be >= 0.  The data of solvers.MLEM and of PDHG(..., data='kl')."""
+    mean = np.asarray(b_true, dtype=np.float64)
+    if peak is not None:
+        mean = float(peak) * mean / mean.max()
+    mean = mean + np.asarray(background, dtype=np.float64)
+    if not np.all(np.isfinite(mean)) or np.any(mean < 0):
+        raise ValueError("poisson_noise: the mean b_true + background must be finite and >= 0")
+    return np.random.default_rng(seed).poisson(mean).astype(np.float64)

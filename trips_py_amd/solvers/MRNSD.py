@@ -8,7 +8,7 @@ With r = b - A x, g = -A^T r and s = -(x . g) (steepest descent in the metric sc
         r -= alpha u ; the next gamma = -<g, s> and bound = min_{s_i < 0} x_i / -s_i, and the reported norms
 Vectors are fp32, scalars and reductions fp64; nothing visits the host unless a stopping rule asks (include/trk.h: the layout of S).
 Not built: sharded MRNSD, a periodic refresh of g from a true product, the s / r updates fused into the blur's two-operand form,
-weighted or Poisson variants, box constraints (solvers.PDHG takes a box).
+weighted variants (Poisson data: solvers.MLEM), box constraints (solvers.PDHG takes a box).
 """
 import numpy as np
 
@@ -16,12 +16,15 @@ from .._io import Formatter, _host, as_operator
 from ._run import IterationRun
 
 
-def default_x0(A, bv):
-    """The constant start sum(b) / sum(A 1) when that is positive, else 1 (a device vector)."""
+def default_x0(A, bv, background=None):
+    """The constant start sum(b) / sum(A 1) when that is positive, else 1 (a device vector).  background (solvers.MLEM): a number or
+    an m-vector on the host that is taken off b first, sum(b - background) / sum(A 1)."""
     eng = A.engine
     ones = eng.to_vec(np.ones(A.shape[1], dtype=np.float32))
     a1 = A.apply(ones)
     sb, sa = float(_host(bv).astype(np.float64).sum()), float(_host(a1).astype(np.float64).sum())
+    if background is not None:
+        sb -= float(np.broadcast_to(np.asarray(background, dtype=np.float64), (A.shape[0],)).sum())
     c = sb / sa if sa != 0.0 else 0.0
     if not (np.isfinite(c) and c > 0.0):
         c = 1.0

@@ -20,13 +20,21 @@ Vectors are fp32, the reported sums fp64 (include/trk.h: the operations and the 
 sigma tau ||K||^2 < 1.
 Not built: the fused space-time kernels for tv='aniso' / 'iso' (SpaceTimeDerivative runs those two on the generic path), time-sharded
 space-time handles and sharded PDHG, rectangular images and frames, fused forms for Framelet2D, cache hints on the fused kernels'
-loads and stores, diagonal preconditioning or adaptive step balancing (`ratio` is the only knob), other data terms.
+loads and stores, diagonal preconditioning or adaptive step balancing (`ratio` is the only knob), data terms other than the two below.
+
+With data='kl' the data term is the Kullback-Leibler fit of Poisson counts, min_x KL(b, A x + background) + lam R(L x) over the box,
+KL(b, y) = sum_i y_i - b_i + b_i log(b_i / y_i) (solvers.MLEM minimises it without a regulariser).  Only the dual update of p changes:
+    p = 1/2 (1 + z - sqrt((z - 1)^2 + 4 sigma b)),  z = p + sigma (w + background)         (trk_pdhg_dual_p_kl)
+the prox of sigma F* for F(y) = KL(b, y + background), F*(p) = sum -b log(1 - p) - background p; every fused TV path comes with it.
 """
 import numpy as np
 
 from .._io import Formatter, _host, as_operator
 from ..operators import operator_norm_sq
 from ._run import IterationRun
+from .MLEM import poisson_data
+
+_GROUPS = {"aniso": 0, "iso": 1, "iso3": 2}        # trk_pdhg_iterate_data's spelling of the grouping
 
 
 def _iso_geometry(L, tv, tv_dims):
@@ -74,11 +82,16 @@ class PDHGRun(IterationRun):
     tv='iso': the isotropic term — sum |L xbar| becomes the sum of the groups' 2-norms; the geometry (N, frames) is
     FirstDerivative2D's (N, 1), SpaceTimeDerivative's (N, nt) or, for any other operator with that row layout, `tv_dims`.
     tv='iso3': the groups (h, v, t) of a voxel on the space-time row layout; fused=None takes the fused space-time kernels where L is
-    a SpaceTimeDerivative with every frame on this rank whose own geometry it is, every other L the unfused dual behind L.apply."""
+    a SpaceTimeDerivative with every frame on this rank whose own geometry it is, every other L the unfused dual behind L.apply.
+    data='kl': the Kullback-Leibler data term with `background` (a number or an m-vector; b and background >= 0, which PDHG()
+    checks) — slot 0 of a row becomes KL(b, A xbar + background), inf where that point leaves the domain of the likelihood."""
 
     def __init__(self, A, b, L, lam, sigma, tau, lower, upper, x0, max_iter, x_true=None, history=True, fused=None, tv="aniso",
-                 tv_dims=None):
+                 tv_dims=None, data="l2", background=0.0):
         A = as_operator(A)
+        if data not in ("l2", "kl"):
+            raise ValueError(f"PDHG: data must be 'l2' or 'kl', not {data!r}")
+        self.data = data
         self.L = L = as_operator(L, "L")
         if A.engine.world > 1:
             raise NotImplementedError("PDHG is not built for unknowns spread over ranks (eng.world > 1)")
@@ -98,6 +111,10 @@ class PDHGRun(IterationRun):
         self.geo = _iso_geometry(L, tv, tv_dims)
         super().__init__(A, b, max_iter, x_true, history, "PDHG xHistory")
         eng, max_iter = self.eng, self.max_iter
+        self.bg = None
+        if data == "kl":
+            bg = _host(background).astype(np.float64)
+            self.bg = float(bg.reshape(-1)[0]) if bg.size == 1 else eng.to_vec(bg, m)       # a number, or a device vector
         if tv == "iso3":                                           # the fused space-time pair groups the rows as its handle lays them out
             from ..operators import SpaceTimeDerivative
             can = bool(isinstance(L, SpaceTimeDerivative) and hasattr(L, "_h") and hasattr(eng, "pdhg_st_dual_iso3")
@@ -140,7 +157,7 @@ class PDHGRun(IterationRun):
         part = self.NP.ref(8 * self.cap * (k - 1))
         x_new = self.hist.row(k - 1)
         A.apply(self.xbar, out=self.w)
-        eng.pdhg_dual_p(self.sigma, self.w, self.bv, self.p, part, self.cap)
+        self._dual_p(self.w, self.p, part)
         if self.fused:
             dual = {"aniso": eng.pdhg_tv_dual, "iso": eng.pdhg_tv_dual_iso, "iso3": eng.pdhg_st_dual_iso3}[self.tv]
             dual(L._h, self.sigma, self.lam, self.xbar, self.q, part, self.cap)
@@ -156,6 +173,12 @@ class PDHGRun(IterationRun):
             eng.pdhg_primal(self.tau, self.lo, self.hi, self.x_cur, self.z, self.v, x_new, self.xbar, self.xt, part, self.cap)
         self.x_cur = x_new
 
+    def _dual_p(self, w, p, part):
+        if self.data == "kl":
+            self.eng.pdhg_dual_p_kl(self.sigma, self.bg, w, self.bv, p, part, self.cap)
+        else:
+            self.eng.pdhg_dual_p(self.sigma, w, self.bv, p, part, self.cap)
+
     def _dual_q(self, u, q, part):
         if self.geo is None:
             self.eng.pdhg_dual_q(self.sigma, self.lam, u, q, part, self.cap)
@@ -165,16 +188,20 @@ class PDHGRun(IterationRun):
             self.eng.pdhg_dual_q_iso(*self.geo, self.sigma, self.lam, u, q, part, self.cap)
 
     def _c_loop(self):
-        """One library call where A and L both have handles (trk_pdhg_iterate, trk_pdhg_iterate_iso, trk_pdhg_iterate_iso3)."""
+        """One library call where A and L both have handles (trk_pdhg_iterate, trk_pdhg_iterate_iso, trk_pdhg_iterate_iso3; data='kl':
+        trk_pdhg_iterate_data)."""
         eng = self.eng
-        loop = {"aniso": "pdhg_iterate", "iso": "pdhg_iterate_iso", "iso3": "pdhg_iterate_iso3"}[self.tv]
+        loop = "pdhg_iterate_data" if self.data == "kl" else \
+            {"aniso": "pdhg_iterate", "iso": "pdhg_iterate_iso", "iso3": "pdhg_iterate_iso3"}[self.tv]
         if not (hasattr(self.A, "_h") and hasattr(self.L, "_h") and hasattr(eng, loop)):
             return None
 
         def call(k_first, n, X, keep):
             rest = (k_first, n, self.sigma, self.tau, self.lam, self.lo, self.hi, self.fused, self.bv, self.p, self.q, self.w, self.u,
                     self.z, self.v, X, keep, self.x_cur, self.xbar, self.xt, self.NP.ref(0), self.cap)
-            if self.geo is None:
+            if self.data == "kl":
+                eng.pdhg_iterate_data(self.A._h, self.L._h, _GROUPS[self.tv], *(self.geo or (0, 0)), 1, self.bg, *rest)
+            elif self.geo is None:
                 eng.pdhg_iterate(self.A._h, self.L._h, *rest)
             else:
                 getattr(eng, loop)(self.A._h, self.L._h, *self.geo, *rest)
@@ -202,16 +229,17 @@ class PDHGRun(IterationRun):
         return float(np.sqrt(self.B.host(0, 1)[0]))
 
     def objective_at(self, x):
-        """1/2 ||A x - b||^2 + lam ||L x||_1 (tv='iso', 'iso3': lam sum_g ||(L x)_g||_2) at a device vector x, from one pair of products (the
-        sums of the dual kernels on scratch duals; the state of the run is left alone)."""
+        """1/2 ||A x - b||^2 + lam ||L x||_1 (tv='iso', 'iso3': lam sum_g ||(L x)_g||_2; data='kl': KL(b, A x + background) in place of
+        the least-squares term, no factor 1/2) at a device vector x, from one pair of products (the sums of the dual kernels on
+        scratch duals; the state of the run is left alone)."""
         eng = self.eng
         w, u = self.A.apply(x), self.L.apply(x)
         part, out = eng.scalars(8 * self.cap), eng.scalars(8)
-        eng.pdhg_dual_p(self.sigma, w, self.bv, eng.zeros(w.numel()), part.ref(0), self.cap)
+        self._dual_p(w, eng.zeros(w.numel()), part.ref(0))
         self._dual_q(u, eng.zeros(u.numel()), part.ref(0))
         eng.finalize_batched(part.ref(0), self.cap, 8, 1, out.ref(0), 8)
         s = out.host()
-        return 0.5 * float(s[0]) + self.lam * float(s[1])
+        return (1.0 if self.data == "kl" else 0.5) * float(s[0]) + self.lam * float(s[1])
 
 
 def pdhg_steps(normK2, ratio=1.0):
@@ -221,7 +249,7 @@ def pdhg_steps(normK2, ratio=1.0):
 
 
 def PDHG(A, b, L, lam, max_iter, tol=0, x0=None, x_true=None, lower=0.0, upper=np.inf, sigma=None, tau=None, normK2=None, ratio=1.0,
-         tv="aniso", tv_dims=None, **kwargs):
+         tv="aniso", tv_dims=None, data="l2", background=0.0, **kwargs):
     """Primal-dual hybrid gradient: min 1/2 ||A x - b||^2 + lam ||L x||_1 subject to lower <= x <= upper.
 
     A, L: LinearOperators with the same column count (L = Identity: plain l1; FirstDerivative2D: anisotropic TV, on fused kernels);
@@ -235,6 +263,12 @@ def PDHG(A, b, L, lam, max_iter, tol=0, x0=None, x_true=None, lower=0.0, upper=n
         SpaceTimeDerivative(N, frames) (its own geometry, on fused kernels; tv_dims for SparseOp(spacetime_derivative(N, N, frames));
         FirstDerivative2D is (N, 1): 'iso' bit for bit).  The groups are triples, the pairs and singles of the volume's three far
         faces, and info['tv'] = 'iso3';
+    data: 'l2' (the least-squares term above) or 'kl' — min KL(b, A x + background) + lam R(L x) over the box, the fit of Poisson
+        counts b (finite and >= 0: ValueError otherwise; clipping Gaussian-noisy data is left to the caller) over a known background
+        (a number or an m-vector, finite and >= 0).  Then `objective` and `objectiveFinal` are KL + lam R with no factor 1/2,
+        info['KL'] = KL(b, A xbar_{k-1} + background) replaces info['Rnrm'] (inf where A xbar + background <= 0 under a count: xbar
+        is not confined to the box; the iteration itself is unaffected), info['data'] = 'kl', and delta= is refused (ValueError: the
+        discrepancy rule is a least-squares notion).  A start with A x0 + background > 0 is advisable (x0 = None is the zero vector);
     b: (m,) / (m,1); x0: (n,) / (n,1) or None (zeros), projected onto the box; lower / upper: scalars, -inf / +inf allowed.
     Steps: sigma and tau as given; if not both are, sigma tau normK2 = 0.95^2 and sigma / tau = ratio, with normK2 the caller's number
     or else operator_norm_sq([A, L], iters=30, seed=0) — an estimate from below, for which the 0.95 leaves room down to 0.9025 of the
@@ -263,6 +297,12 @@ def PDHG(A, b, L, lam, max_iter, tol=0, x0=None, x_true=None, lower=0.0, upper=n
     if L.shape[1] != A.shape[1]:
         raise ValueError(f"L has {L.shape[1]} columns, A has {A.shape[1]}")
     _iso_geometry(L, tv, tv_dims)                # refused before the norm estimate is paid for
+    if data not in ("l2", "kl"):
+        raise ValueError(f"PDHG: data must be 'l2' or 'kl', not {data!r}")
+    if data == "kl":
+        _bh, background = poisson_data(b, background, A.shape[0], "PDHG(data='kl')")
+        if kwargs.get("delta", None) is not None:
+            raise ValueError("PDHG(data='kl'): delta= is refused — the discrepancy rule is a least-squares notion")
     lam = float(lam)
     if not (np.isfinite(lam) and lam >= 0):
         raise ValueError("PDHG: lam must be finite and >= 0")
@@ -280,7 +320,7 @@ def PDHG(A, b, L, lam, max_iter, tol=0, x0=None, x_true=None, lower=0.0, upper=n
     delta = kwargs.get("delta", None)
     eta = float(kwargs.get("eta", 1.01))
     run = PDHGRun(A, b, L, lam, sigma, tau, lower, upper, x0, max_iter, x_true, kwargs.get("history", True), kwargs.get("fused", None),
-                  tv, tv_dims)
+                  tv, tv_dims, data, background)
     if tol == 0 and delta is None:
         run.run(max_iter)                       # nothing is read back inside the loop -> one enqueue
     else:
@@ -294,10 +334,11 @@ def PDHG(A, b, L, lam, max_iter, tol=0, x0=None, x_true=None, lower=0.0, upper=n
     rows = run.rows()
     k, x_fin = run.k, run.x_cur
     with np.errstate(divide="ignore", invalid="ignore"):
+        fit = {"KL": list(rows[:, 0]), "data": "kl"} if data == "kl" else {"Rnrm": list(np.sqrt(rows[:, 0]) / run.b_norm())}
         info = {"xHistory": run.hist.collect(fmt, k), "its": k,
                 "relResidual": list(np.sqrt(rows[:, 5]) / np.sqrt(rows[:, 4])),
-                "Rnrm": list(np.sqrt(rows[:, 0]) / run.b_norm()),
-                "objective": list(0.5 * rows[:, 0] + lam * rows[:, 1]),
+                **fit,
+                "objective": list((1.0 if data == "kl" else 0.5) * rows[:, 0] + lam * rows[:, 1]),
                 "dualChange": list(np.sqrt(rows[:, 2] + rows[:, 3])),
                 "active": [int(c) for c in rows[:, 7]],
                 "sigma": float(sigma), "tau": float(tau), "normK2": None if normK2 is None else float(normK2),
