@@ -1105,12 +1105,14 @@ int trk_halo_exchange2(trk_comm* comm, const float* send_prev, float* recv_prev,
  *
  * trk_dot_pair: out3[0] = sum q*q, out3[1] = sum q*w, out3[2] = sum w*w (w may be NULL: 0, 0) — local sums, one pass, fp64.
  * trk_cgls_sharded_update: from the all-reduced G4 and *gamma_prev (= gamma_{k-2}; unused when `first`):
- *   p = t + beta p; w = q + beta w (first: p = t, w = q); x_new = x + alpha p; r -= alpha w, alpha = gamma_{k-1} / delta_k;
- *   *publish_delta = delta_k, *publish_gamma = gamma_{k-1}; the rank's share of ||x_new||^2, ||alpha p||^2, ||x_new - x_true||^2
- *   (CGLS.py:76-80) as *n_blocks x 3 block partials (trk_finalize_batched, then one sum over the ranks after the solve).
+ *   p = fmaf(beta, p, t); w = fmaf(beta, w, q) (first: p = t, w = q, the old p and w are not read); x_new = fmaf(alpha, p, x);
+ *   r = fmaf(-alpha, w, r): ONE rounding per entry, beta = (float)(gamma_{k-1} / gamma_{k-2}), alpha = (float)(gamma_{k-1} / delta_k);
+ *   *publish_delta = delta_k, *publish_gamma = gamma_{k-1}; the rank's share of ||x_new||^2, ||alpha p||^2 (summed from
+ *   fl32(alpha p), a rounding of its own), ||x_new - x_true||^2 (CGLS.py:76-80) as *n_blocks x 3 block partials
+ *   (trk_finalize_batched, then one sum over the ranks after the solve).  x_new may be x; it must not be p or t.
  * trk_cgls_sharded_scalars: G4[1..3] as trk_dot_pair, and G4[0] = the sum of the n_gamma raw block partials of ||t||^2 the adjoint
  *   apply left (trk_op_apply_fused with x2 = NULL; n_gamma = 0: G4[0] is finished already) — by ONE workgroup for a rank's share of
- *   up to 2^19 samples (three launches less per iteration), else by trk_dot_pair + a finalize.
+ *   up to 2^14 samples and n_gamma <= 2^16 (three launches less per iteration), else by trk_dot_pair's kernel + one finalize of all four.
  * trk_cgls_iterate_sharded: n_iters iterations enqueued by one call — q = A t; trk_cgls_sharded_scalars; trk_allreduce_f64(comm, G4, 4)
  *   (skipped for comm = NULL); trk_cgls_sharded_update; t = A^T r.  Scalar layout as trk_cgls_iterate: S[0] = gamma_0, S[5k] =
  *   delta_k, S[5k+1] = gamma_k (gamma_k is published by iteration k+1).  PG / pcap / *n_g_inout (may be NULL / 0 / NULL): with them

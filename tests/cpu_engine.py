@@ -192,7 +192,7 @@ class CpuEngine:
         p.copy_(torch.from_numpy(pn))
         w.copy_(torch.from_numpy(wn))
         d = a32 * pn
-        xn = (x.numpy() + d).astype(np.float32)
+        xn = (x.numpy() + d).astype(np.float32)            # two roundings; the device's x' is the one-rounding fmaf(alpha, p', x) (trk.h)
         x_new.copy_(torch.from_numpy(xn))
         r.copy_(torch.from_numpy((r.numpy() - a32 * wn).astype(np.float32)))
         _put(pub_delta, delta)

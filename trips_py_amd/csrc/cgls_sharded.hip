@@ -9,8 +9,11 @@
 // carried over as delta_{k-1}: the expansion is then that of the very w_k the update forms, and no error compounds through beta^2):
 //     beta = gamma_{k-1} / gamma_{k-2} (0 for k = 1);  p_k = t_{k-1} + beta p_{k-1};  w_k = q + beta w_{k-1};
 //     alpha = gamma_{k-1} / delta_k;  x_k = x_{k-1} + alpha p_k;  r_k = r_{k-1} - alpha w_k;  t_k = A^T r_k.
+// Per entry every update is ONE rounding: p_k = fmaf(beta, p, t), w_k = fmaf(beta, w, q), x_k = fmaf(alpha, p_k, x), r_k = fmaf(-alpha, w_k, r),
+// written as fmaf so that none rests on the compiler's contraction; ||alpha p_k||^2 is summed from d = fl32(alpha p_k).
 // Same operator applies per iteration (one A, one A^T), same iterates in exact arithmetic; in floating point w_k carries the
-// rounding of its recurrence instead of that of a fresh product (tests: iterates within 1e-5 of the two-reduction form).
+// rounding of its recurrence instead of that of a fresh product (tests: iterates within 1e-5 of the two-reduction form; every
+// kernel here entry by entry against float64, tests/test_gpu_sharded_entrywise.py).
 // The three norms the reference records per iterate (CGLS.py:76-80) are only REPORTED with tol = 0, so they stay local block
 // partials and are summed over blocks and ranks once, after the solve.
 #include "trk_internal.h"
@@ -157,7 +160,7 @@ __global__ __launch_bounds__(NT) void k_cgls_sharded_update(int64_t n, int64_t m
       }
       st4(p, i, pv);
       const float4 d = make_float4(alpha * pv.x, alpha * pv.y, alpha * pv.z, alpha * pv.w);
-      const float4 xn = make_float4(xv.x + d.x, xv.y + d.y, xv.z + d.z, xv.w + d.w);
+      const float4 xn = make_float4(fmaf(alpha, pv.x, xv.x), fmaf(alpha, pv.y, xv.y), fmaf(alpha, pv.z, xv.z), fmaf(alpha, pv.w, xv.w));
       st4(x_new, i, xn);
       acc[0] += (double)xn.x * xn.x + (double)xn.y * xn.y + (double)xn.z * xn.z + (double)xn.w * xn.w;
       acc[1] += (double)d.x * d.x + (double)d.y * d.y + (double)d.z * d.z + (double)d.w * d.w;
@@ -186,7 +189,7 @@ __global__ __launch_bounds__(NT) void k_cgls_sharded_update(int64_t n, int64_t m
   for (int64_t i = ntail + tid; i < n; i += nth) {
     const float pv = first ? t[i] : fmaf(beta, p[i], t[i]);
     p[i] = pv;
-    const float d = alpha * pv, xn = x[i] + d;
+    const float d = alpha * pv, xn = fmaf(alpha, pv, x[i]);
     x_new[i] = xn;
     acc[0] += (double)xn * xn;
     acc[1] += (double)d * d;
