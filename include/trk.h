@@ -702,6 +702,58 @@ int trk_mlem_iterate(trk_op* A, int k_first, int n_iters, double bg, const float
                      float* t, float* X, int64_t x_ld, int keep_history, const float* x_prev, const float* x_true, double* NP,
                      int np_capacity_blocks, trk_stream stream);
 
+/* ---------------------------------------------------------------- Ordered subsets: OSEM, SIRT / OS-SIRT / SART --- */
+/* Row-action iterations over an operator cut into S ROW SUBSETS: ops[s] (a handle of its own) maps x to the rows of subset s, and
+ * every data-side vector (b, bg_vec, RINV) is held SUBSET-MAJOR, subset s at [row_off[s], row_off[s+1]).  A PASS visits the subsets
+ * in `order` (a permutation of 0 .. S-1); a SUB-STEP on subset s is
+ *   w = A_s x ;  one kernel over the subset's data -> rho (written over w) ;  t = A_s^T rho ;  one kernel over the unknowns.
+ * OSEM (Poisson data, x >= 0; S = 1 is MLEM):  rho = b_s / (w + bg_s) by trk_mlem_ratio ;  x' = x . t . sinv_s,  sinv_s from
+ *   s_s = A_s^T 1 by trk_mlem_sinv (row s of SINV).
+ * SIRT (least squares in a box; S = 1 is SIRT, S > 1 OS-SIRT, one view per subset SART):
+ *   x' = P_box(x + omega C_s A_s^T R_s (b_s - A_s x)),  R_s = 1 / (A_s 1) (RINV, subset-major),  C_s = 1 / (A_s^T 1) (row s of CINV),
+ *   both by trk_mlem_sinv: 0 where the sum is not positive.  RINV = CINV = NULL: the Landweber step x' = P_box(x + omega A^T (b - A x)).
+ * Vectors fp32, sums fp64, no atomics.  omega, lo, hi are rounded to fp32 once on the host (omf, lof, hif; -inf / +inf bounds are
+ * allowed).  The fp32 operations, in this order, the one multiply-add an fmaf, nothing else contracted:
+ *   osem update:    x' = (sinv > 0) ? fmaxf((x * t) * sinv, 0) : x ;  d = x' - (x_ref ? x_ref : x)
+ *   sirt residual:  d = b - w ;  rho = rinv ? d * rinv : d
+ *   sirt update:    u = cinv ? t * cinv : t ;  x' = fminf(fmaxf(fmaf(omf, u, x), lof), hif) ;  d = x' - (x_ref ? x_ref : x)
+ * THE KEEP RULE: an unknown the CURRENT subset does not see (sinv == 0) keeps its value in the OSEM update — trk_mlem_update would
+ * set it to 0, and a multiplicative iteration never moves a 0 again.  An unknown NO subset sees therefore stays at its start value
+ * (MLEM sets it to 0).  In the SIRT update cinv == 0 gives u = 0: the same rule by arithmetic.
+ * Sums: block partials in PDHG's rows of 8 (as MLEM's above), the two kernels of a sub-step share one zeroed block of
+ * 8 * capacity_blocks doubles:
+ *   [ OSEM: KL(b_s, w + bg_s)  | SIRT: ||b_s - w||^2 (d^2 in fp64),
+ *     OSEM: ||w + bg_s - b_s||^2 | SIRT: sum rho d in fp64 = ||b_s - w||^2 in the R-weighted norm,
+ *     0, 0, ||x'||^2, ||d||^2, ||x' - x_true||^2 (0 without x_true),
+ *     OSEM: the number of entries of x' equal to 0 | SIRT: the number of entries of x' that ended on a FINITE bound ]
+ *
+ * trk_osem_update (slots 4..7), trk_sirt_residual (slots 0, 1; rho may be w and nothing else), trk_sirt_update (slots 4..7): streaming
+ *   kernels, 16-byte accesses where every operand is 16-byte aligned; x_new may be x and nothing else.  *n_blocks: the blocks that wrote.
+ * trk_subsets_blocks: the largest block count of a sub-step's kernels, m_max the rows of the largest subset.
+ * trk_osem_iterate, trk_sirt_iterate: passes k_first .. k_first + n_iters - 1 enqueued by one call, nothing read back; 4 S launches
+ *   each.  ops, order (S ints) and row_off (S + 1 offsets, from 0, increasing) are HOST arrays.  Pass k takes its start iterate from
+ *   x_prev (k = k_first) or the slot pass k-1 wrote, and writes iterate k to slot k-1 of X (keep_history) or (k-1) & 1.  Its first
+ *   sub-step reads the start iterate and writes the scratch xw (n floats; not needed for S = 1), the middle ones update xw in place,
+ *   the last one reads xw and writes the slot with x_ref = the start iterate and with x_true: its slot 5 is ||x_k - x_{k-1}||^2 over
+ *   the whole pass.  With S = 1 the one sub-step goes from the start iterate to the slot, x_ref = NULL.  w holds the rows of the
+ *   largest subset.  Sub-step j = (k-1) S + position writes its partials at NP + 8 np_capacity_blocks j (zeroed by the caller);
+ *   trk_finalize_batched over iterations * S batches yields the sub-step rows.  The same kernels as stepping: the same bits. */
+int trk_subsets_blocks(int64_t m_max, int64_t n, int* blocks);
+int trk_osem_update(int64_t n, const float* x, const float* t, const float* sinv, const float* x_ref, const float* x_true, float* x_new,
+                    double* partials, int capacity_blocks, int* n_blocks, trk_stream stream);
+int trk_sirt_residual(int64_t m, const float* rinv, const float* w, const float* b, float* rho, double* partials, int capacity_blocks,
+                      int* n_blocks, trk_stream stream);
+int trk_sirt_update(int64_t n, double omega, double lo, double hi, const float* x, const float* t, const float* cinv, const float* x_ref,
+                    const float* x_true, float* x_new, double* partials, int capacity_blocks, int* n_blocks, trk_stream stream);
+int trk_osem_iterate(trk_op* const* ops, int S, const int* order, const int64_t* row_off, int k_first, int n_iters, double bg,
+                     const float* bg_vec, const float* b, const float* SINV, int64_t sinv_ld, float* w, float* t, float* xw, float* X,
+                     int64_t x_ld, int keep_history, const float* x_prev, const float* x_true, double* NP, int np_capacity_blocks,
+                     trk_stream stream);
+int trk_sirt_iterate(trk_op* const* ops, int S, const int* order, const int64_t* row_off, int k_first, int n_iters, const float* b,
+                     const float* RINV, const float* CINV, int64_t cinv_ld, double omega, double lo, double hi, float* w, float* t,
+                     float* xw, float* X, int64_t x_ld, int keep_history, const float* x_prev, const float* x_true, double* NP,
+                     int np_capacity_blocks, trk_stream stream);
+
 /* ---------------------------------------------------------------- PDHG: TV / l1 under box constraints --- */
 /* The primal-dual hybrid gradient iteration (Chambolle and Pock 2011, algorithm 1, theta = 1) for
  *   min_x  1/2 ||A x - b||^2 + lam ||L x||_1   subject to  lo <= x <= hi.

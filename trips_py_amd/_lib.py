@@ -17,7 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 INCLUDE = os.path.join(os.path.dirname(HERE), "include")
 LIB_PATH = os.path.join(CSRC, "libtrk.so")
-SOURCES = ["core.hip", "vecops.hip", "blur2d.hip", "blur_tile.hip", "gemv.hip", "wgram.hip", "tvops.hip", "radon2d.hip", "radon_fwd.hip", "radon_adj.hip", "spmv.hip", "framelet2d.hip", "fanbeam2d.hip", "projected.hip", "host_regparam.hip", "host_worker.hip", "hybrid_host.hip", "cgls_update.hip", "cgls_loop.hip", "mrnsd.hip", "mlem.hip", "pdhg.hip", "pdhg_tv.hip", "comm.hip", "cgls_tiled.hip", "cgls_sharded.hip", "ref64.hip", "dense_svd.hip"]
+SOURCES = ["core.hip", "vecops.hip", "blur2d.hip", "blur_tile.hip", "gemv.hip", "wgram.hip", "tvops.hip", "radon2d.hip", "radon_fwd.hip", "radon_adj.hip", "spmv.hip", "framelet2d.hip", "fanbeam2d.hip", "projected.hip", "host_regparam.hip", "host_worker.hip", "hybrid_host.hip", "cgls_update.hip", "cgls_loop.hip", "mrnsd.hip", "mlem.hip", "subsets.hip", "pdhg.hip", "pdhg_tv.hip", "comm.hip", "cgls_tiled.hip", "cgls_sharded.hip", "ref64.hip", "dense_svd.hip"]
 HIPCC_FLAGS = ["-O3", "--offload-arch=gfx950", "-std=c++17", "-fPIC", "-I" + INCLUDE, "-I" + CSRC]
 
 

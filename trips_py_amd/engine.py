@@ -738,6 +738,45 @@ class HipEngine:
                 NP, int(np_cap))
         _lib.check(self.lib.trk_mlem_iterate(*map(_ptr, args), self.stream()), "trk_mlem_iterate")
 
+    # ------------------------------------------------------------------ ordered subsets: OSEM, SIRT (subsets.hip; the operations: include/trk.h)
+    def subsets_blocks(self, m_max, n):
+        """The largest block count of a sub-step's kernels (m_max: the rows of the largest subset)."""
+        return self._pdhg("trk_subsets_blocks", int(m_max), int(n), stream=False)
+
+    def osem_update(self, x, t, sinv, x_ref, x_true, x_new, partials, capacity):
+        """x_new = max(x t sinv, 0) where sinv > 0, else x (x_new may be x); d = x_new - (x_ref or x); slots 4..7.  Returns the block count."""
+        return self._pdhg("trk_osem_update", x.numel(), x, t, sinv, x_ref, x_true, x_new, partials, int(capacity))
+
+    def sirt_residual(self, rinv, w, b, rho, partials, capacity):
+        """rho = (b - w) rinv (rho may be w; rinv None: b - w); slots 0, 1.  Returns the block count."""
+        return self._pdhg("trk_sirt_residual", w.numel(), rinv, w, b, rho, partials, int(capacity))
+
+    def sirt_update(self, omega, lo, hi, x, t, cinv, x_ref, x_true, x_new, partials, capacity):
+        """x_new = clip(x + omega t cinv, lo, hi) (x_new may be x; cinv None: t alone); slots 4..7.  Returns the block count."""
+        return self._pdhg("trk_sirt_update", x.numel(), float(omega), float(lo), float(hi), x, t, cinv, x_ref, x_true, x_new, partials,
+                          int(capacity))
+
+    @staticmethod
+    def _subset_args(handles, order, row_off):
+        """The three host arrays of the one-call loops (ctypes arrays pass as pointers and must outlive the call only)."""
+        S = len(handles)
+        return ((ctypes.c_void_p * S)(*[getattr(h, "value", h) for h in handles]), S, (ctypes.c_int * len(order))(*map(int, order)),
+                (ctypes.c_int64 * len(row_off))(*map(int, row_off)))
+
+    def osem_iterate(self, handles, order, row_off, k_first, n_iters, bg, b, SINV, w, t, xw, X, keep, x_prev, x_true, NP, np_cap):
+        """n_iters OSEM passes over the subsets in one library call (SINV: [S, n], row s the reciprocals of subset s)."""
+        args = (*self._subset_args(handles, order, row_off), int(k_first), int(n_iters), *self._background(bg), b, SINV, SINV.stride(0), w,
+                t, xw, X, X.stride(0), int(bool(keep)), x_prev, x_true, NP, int(np_cap))
+        _lib.check(self.lib.trk_osem_iterate(*map(_ptr, args), self.stream()), "trk_osem_iterate")
+
+    def sirt_iterate(self, handles, order, row_off, k_first, n_iters, b, RINV, CINV, omega, lo, hi, w, t, xw, X, keep, x_prev, x_true,
+                     NP, np_cap):
+        """n_iters SIRT passes over the subsets in one library call (RINV subset-major, CINV [S, n]; both None: Landweber)."""
+        args = (*self._subset_args(handles, order, row_off), int(k_first), int(n_iters), b, RINV, CINV,
+                0 if CINV is None else CINV.stride(0), float(omega), float(lo), float(hi), w, t, xw, X, X.stride(0), int(bool(keep)),
+                x_prev, x_true, NP, int(np_cap))
+        _lib.check(self.lib.trk_sirt_iterate(*map(_ptr, args), self.stream()), "trk_sirt_iterate")
+
     # ------------------------------------------------------------------ PDHG (pdhg.hip, pdhg_tv.hip; the rows of 8 partials: include/trk.h)
     def _pdhg(self, name, *args, stream=True):
         """One library call of the PDHG family that reports an int (a block count) through its last pointer: a tensor goes as its

@@ -794,6 +794,113 @@ class VStack(LinearOperator):
             eng.nrm2sq(y2[0], sumsq)
 
 
+def bit_reversed_order(S):
+    """The subsets 0 .. S-1 sorted by the bit-reversed value of their number in ceil(log2 S) bits: consecutive sub-steps then see
+    views far apart.  S = 6: 0, 4, 2, 1, 5, 3."""
+    bits = max(1, (int(S) - 1).bit_length())
+    return sorted(range(int(S)), key=lambda s: int(format(s, f"0{bits}b")[::-1], 2))
+
+
+class RowSubsets(LinearOperator):
+    """An operator cut into S row subsets, each an operator of the engine of its own: what the ordered-subsets solvers (solvers.OSEM,
+    solvers.SIRT / SART) iterate over.
+
+        ops      S operators; ops[s] maps the same x to the rows `rows[s]` of A
+        rows     S index arrays into A's rows, together a partition of range(m)
+        perm     the concatenation of `rows` in subset order: data are held on the device SUBSET-MAJOR, b[perm]
+        offsets  S + 1 row offsets into that order
+        order    the order in which a pass visits the subsets
+
+    Radon2DParallel and FanBeam2D: subset s holds the views s, s + S, s + 2S, ... — a new handle made from angles[s::S] with the same
+    detector, scale and geometry; 1 <= S <= n_ang, S need not divide n_ang.  SparseOp: S an int (rows s::S) or a list of index arrays
+    that partition the rows; each subset is a SparseOp of matrix[rows].  Any other operator (blur, block-diagonal and dynamic
+    operators, framelets, first differences) has no views to deal out and raises ValueError for S > 1; S = 1 wraps A itself.
+
+    order: "bitrev" (bit_reversed_order), "sequential", or a permutation of range(S).
+
+    THE SUBSET HANDLES ARE NOT SLICES OF THE FULL OPERATOR'S BITS.  A parallel-beam handle chooses its adjoint's neighbour constants by
+    error diffusion over the angles it was made with, and its forward groups symmetric angles: ops[s] agrees with the rows of A to
+    rounding, not bit for bit.  Tests therefore compare each subset handle with the float64 operator of ITS angles.
+
+    As a LinearOperator this is the subset-major stack A[perm] (the subsets applied one after the other)."""
+
+    def __init__(self, A, S, order="bitrev"):
+        m = A.shape[0]
+        if not isinstance(S, (int, np.integer)):
+            if type(A) is not SparseOp:
+                raise ValueError("RowSubsets: subsets given as index arrays need a SparseOp")
+            rows = [np.asarray(r, dtype=np.int64).reshape(-1) for r in S]
+        elif S == 1:
+            self._setup([A], [np.arange(m)], m, order, A)
+            return
+        elif isinstance(A, (Radon2DParallel, FanBeam2D)):
+            n_ang = len(A.angles)
+            if not 1 <= S <= n_ang:
+                raise ValueError(f"RowSubsets: need 1 <= S <= the {n_ang} views of the operator, got S = {S}")
+            if isinstance(A, Radon2DParallel):
+                ops = [Radon2DParallel(A.N, A.angles[s::S], n_det=A.n_det, scale=A.scale, engine=A.engine) for s in range(S)]
+            else:
+                ops = [FanBeam2D(A.N, angles=A.angles[s::S], n_det=A.n_det, source_origin=A.sod, origin_detector=A.odd, det_pitch=A.pitch,
+                                 engine=A.engine) for s in range(S)]
+            views = np.arange(m).reshape(n_ang, A.n_det)
+            self._setup(ops, [views[s::S].reshape(-1) for s in range(S)], m, order, A)
+            return
+        elif type(A) is SparseOp:
+            if not 1 <= S <= m:
+                raise ValueError(f"RowSubsets: need 1 <= S <= the {m} rows of the matrix, got S = {S}")
+            rows = [np.arange(s, m, S) for s in range(S)]
+        else:
+            raise ValueError(f"RowSubsets: a {type(A).__name__} has no views or rows to deal out into S = {S} subsets (built for "
+                             "Radon2DParallel, FanBeam2D and SparseOp; S = 1 works for every operator)")
+        self._partition(rows, m)                                  # before matrix[rows] trips over a bad index
+        self._setup([SparseOp(A.matrix[r], engine=A.engine) for r in rows], rows, m, order, A)
+
+    @classmethod
+    def from_ops(cls, ops, rows, m, order="bitrev"):
+        """From subset operators the caller made: ops[s] stands for the rows `rows[s]` of an m-row operator."""
+        self = cls.__new__(cls)
+        self._setup(list(ops), [np.asarray(r, dtype=np.int64).reshape(-1) for r in rows], int(m), order, None)
+        return self
+
+    @staticmethod
+    def _partition(rows, m):
+        perm = np.concatenate(rows) if len(rows) else np.empty(0, dtype=np.int64)
+        if perm.size != m or not np.array_equal(np.sort(perm), np.arange(m)):
+            raise ValueError(f"RowSubsets: the index arrays do not partition the {m} rows")
+        return perm
+
+    def _setup(self, ops, rows, m, order, A):
+        S = len(ops)
+        if S < 1 or len(rows) != S:
+            raise ValueError("RowSubsets: need one index array per subset operator, and at least one subset")
+        perm = self._partition(rows, m)
+        if any(o.shape != (len(r), ops[0].shape[1]) or len(r) == 0 for o, r in zip(ops, rows)):
+            raise ValueError("RowSubsets: every subset operator needs the rows of its index array (at least one) and the same columns")
+        if isinstance(order, str):
+            if order not in ("bitrev", "sequential"):
+                raise ValueError(f"RowSubsets: order is 'bitrev', 'sequential' or a permutation, got {order!r}")
+            order = bit_reversed_order(S) if order == "bitrev" else range(S)
+        self.order = [int(s) for s in order]
+        if sorted(self.order) != list(range(S)):
+            raise ValueError(f"RowSubsets: order is not a permutation of range({S})")
+        self.A, self.ops, self.rows, self.perm = A, ops, rows, perm
+        self.offsets = np.concatenate(([0], np.cumsum([len(r) for r in rows]))).astype(np.int64)
+        self._ro, self._tmp = self.offsets, None                  # what VStack._apply works with
+        super().__init__((m, ops[0].shape[1]), ops[0].engine)
+
+    _apply = VStack._apply
+
+    def split(self, b):
+        """A host m-vector in subset-major order, b[perm]."""
+        return np.asarray(b).reshape(-1)[self.perm]
+
+    def join(self, y):
+        """The inverse of split."""
+        out = np.empty_like(np.asarray(y).reshape(-1))
+        out[self.perm] = np.asarray(y).reshape(-1)
+        return out
+
+
 class Identity(LinearOperator):
     def __init__(self, n, engine=None):
         super().__init__((n, n), engine)

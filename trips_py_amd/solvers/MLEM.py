@@ -9,7 +9,7 @@ adjoint the method is defined with that transpose, as MRNSD's is.  Per iteration
 No device scalar steers the loop, so a whole solve is one enqueue (trk_mlem_iterate).  Vectors are fp32, the reported sums fp64
 (include/trk.h: the operations and the layout of S).  An unknown no datum sees (s_i = 0: a masked detector) is set to 0 by the first
 iteration and stays there; where A x + beta <= 0 under a positive count the ratio is taken as 0 and KL reports inf.
-Not built: ordered subsets, sharded MLEM, the ratio fused into the operator's epilogue, acceleration or line search, KL for MMGKS
+Ordered subsets: solvers.OSEM.  Not built: sharded MLEM, the ratio fused into the operator's epilogue, acceleration or line search, KL for MMGKS
 (solvers.PDHG takes data='kl' for a regularised fit).
 """
 import numpy as np

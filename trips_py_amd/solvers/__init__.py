@@ -3,6 +3,8 @@
 from .CGLS import CGLS, CGLSRun, CGLSRunFused, CGLSRunSharded  # noqa: F401
 from .MRNSD import MRNSD, MRNSDRun  # noqa: F401
 from .MLEM import MLEM, MLEMRun, RichardsonLucy  # noqa: F401
+from .OSEM import OSEM, OSEMRun  # noqa: F401
+from .SIRT import SART, SIRT, SIRTRun  # noqa: F401
 from .PDHG import PDHG, PDHGRun  # noqa: F401
 from .Hybrid_LSQR import Hybrid_LSQR  # noqa: F401
 from .Hybrid_GMRES import Hybrid_GMRES  # noqa: F401

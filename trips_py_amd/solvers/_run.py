@@ -1,6 +1,9 @@
 """What the iteration runs of CGLS, MRNSD and PDHG share: the operands on the device, the history of the iterates, and the two ways
 of driving the recurrence — `step()` by `step()` from Python, or `run(n)` as one library call per stretch."""
-from .._io import History, as_operator
+import numpy as np
+import torch
+
+from .._io import History, _host, as_operator
 
 
 class _ShiftedRows:
@@ -79,3 +82,100 @@ class IterationRun:
             self.k += c
             n_steps -= c
             self.x_cur = self.slot(self.k - 1)                     # what the next chunk starts from
+
+
+class SubsetRun(IterationRun):
+    """What the ordered-subsets runs (OSEMRun, SIRTRun) share.  An iteration is a PASS over the S row subsets of an
+    operators.RowSubsets in its visiting order; sub-step `pos` of pass k is w = A_s x, the run's data kernel on the subset's slice of
+    the subset-major data (rho over w), t = A_s^T rho, and the run's update kernel.  The first sub-step reads the pass's start iterate
+    and writes the scratch xw, the middle ones update xw in place, the last one writes the history slot with x_ref = the start iterate
+    and with x_true (include/trk.h).  A run gives `_data(s, w, lo, hi, part)` and `_update(s, x_in, x_ref, x_true, x_out, part)`.
+
+    Sub-step j = (k - 1) S + pos owns the rows of partials at NP + 8 cap j.  Row k of the PASS: slots 0 and 1 are the sums of the S
+    sub-steps' slots, added on the host in visiting order — RUNNING values, each subset's term taken at the sub-iterate that subset
+    saw, not at one common point; slots 4 to 7 are the last sub-step's (||x_k||^2, ||x_k - x_{k-1}||^2 over the whole pass,
+    ||x_k - x_true||^2, the run's count)."""
+
+    def __init__(self, A, b, max_iter, x_true, history, what, subsets, order):
+        from ..operators import RowSubsets
+        sub = subsets if isinstance(subsets, RowSubsets) else RowSubsets(as_operator(A), subsets, order)
+        if A is not None and tuple(A.shape) != sub.shape:
+            raise ValueError(f"the subsets stand for a {sub.shape[0]} x {sub.shape[1]} operator, A is {A.shape[0]} x {A.shape[1]}")
+        if sub.engine.world > 1:
+            raise NotImplementedError(f"{what.split()[0]} is not built for unknowns spread over ranks (eng.world > 1)")
+        bh = _host(b).reshape(-1)
+        if bh.size != sub.shape[0]:
+            raise ValueError(f"b has {bh.size} entries, expected {sub.shape[0]}")
+        super().__init__(sub, sub.split(bh), max_iter, x_true, history, what)        # bv: subset-major
+        eng, self.sub, self.nS = self.eng, sub, len(sub.ops)
+        m_max, n = max(len(r) for r in sub.rows), sub.shape[1]
+        self.w, self.t = eng.empty(m_max), eng.empty(n)
+        self.xw = eng.empty(n) if self.nS > 1 else None
+        self.cap = eng.subsets_blocks(m_max, n)
+        self.NP = eng.scalars(8 * self.cap * self.max_iter * self.nS)    # zeroed: a kernel writes only its slots of its blocks' rows
+        self.SS = eng.scalars(8 * self.max_iter * self.nS)               # the sub-step rows
+        self.B = eng.scalars(1)                                          # ||b||^2
+        eng.nrm2sq(self.bv, self.B.ref(0))
+        self._final = 0
+
+    def subset_sums(self, transpose):
+        """A_s 1 for every subset, subset-major in one m-vector — or, transposed, A_s^T 1 as the rows of an [S, n] block."""
+        eng, sub = self.eng, self.sub
+        if transpose:
+            out = eng.empty_basis(self.nS, sub.shape[1])
+            for s, op in enumerate(sub.ops):
+                op.apply(eng.to_vec(np.ones(op.shape[0], dtype=np.float32)), out=out[s], transpose=True)
+            return out
+        ones = eng.to_vec(np.ones(sub.shape[1], dtype=np.float32))
+        return torch.cat([op.apply(ones) for op in sub.ops])
+
+    def _step(self):
+        sub, S = self.sub, self.nS
+        self.k += 1
+        for pos, s in enumerate(sub.order):
+            first, last = pos == 0, pos == S - 1
+            x_in = self.x_cur if first else self.xw
+            x_out = self.hist.row(self.k - 1) if last else self.xw
+            part = self.NP.ref(8 * self.cap * ((self.k - 1) * S + pos))
+            lo, hi = int(sub.offsets[s]), int(sub.offsets[s + 1])
+            w = self.w[:hi - lo]
+            sub.ops[s].apply(x_in, out=w)
+            self._data(s, w, lo, hi, part)                                            # rho over w
+            sub.ops[s].apply(w, out=self.t, transpose=True)
+            self._update(s, x_in, self.x_cur if last and not first else None, self.xt if last else None, x_out, part)
+        self.x_cur = x_out
+
+    def _subset_args(self):
+        """(handles, order, row offsets) for the one-call loops, or None where a subset has no handle."""
+        if not all(hasattr(o, "_h") for o in self.sub.ops):
+            return None
+        return [o._h for o in self.sub.ops], self.sub.order, self.sub.offsets
+
+    def _finish(self):
+        """The block partials of the passes not summed yet into their sub-step rows."""
+        if self._final == self.k:
+            return
+        f, S = self._final, self.nS
+        self.eng.finalize_batched(self.NP.ref(8 * self.cap * f * S), self.cap, 8, (self.k - f) * S, self.SS.ref(8 * f * S), 8)
+        self._final = self.k
+
+    def substep_rows(self, k_from=1):
+        """[k - k_from + 1, S, 8] on the host: the rows of the sub-steps of passes k_from .. k, in visiting order (host sync)."""
+        self._finish()
+        return self.SS.host(8 * (k_from - 1) * self.nS, 8 * self.k * self.nS).reshape(-1, self.nS, 8)
+
+    def rows(self, k_from=1):
+        """The rows of passes k_from .. k on the host."""
+        sr = self.substep_rows(k_from)
+        out = sr[:, -1, :].copy()
+        out[:, :4] = 0.0
+        for pos in range(self.nS):                                                    # in visiting order, always the same association
+            out[:, :2] += sr[:, pos, :2]
+        return out
+
+    def row(self, k):
+        """Pass row k, 1-based (host sync); k = self.k reads back that pass alone."""
+        return self.rows(k)[0]
+
+    def b_norm(self):
+        return float(np.sqrt(self.B.host(0, 1)[0]))
